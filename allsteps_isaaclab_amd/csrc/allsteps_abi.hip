@@ -206,6 +206,7 @@ int as_create(int32_t num_envs, const as_model_t* model, const as_sim_t* sim, co
     }
   if (!as::step_supported_nv(h.nv))
     return fail(AS_ERR_INVALID, "as_create: no k_step instantiation for " + std::to_string(h.nv) + " dofs");
+  as::fill_lane_table(h);
 
   as_env* env = new as_env();
   env->n = num_envs;
@@ -411,6 +412,7 @@ int as_set_actuator(as_env_t* env, const as_actuator_t* act) {
     return fail(AS_ERR_INVALID, "as_set_actuator: the DC motor needs velocity_limit > 0 and effort_limit >= 0");
   HIP_TRY(hipSetDevice(env->device));
   env->host.act = *act;
+  as::fill_lane_table(env->host);
   // ordered on the null stream with respect to every earlier launch (hipMemcpy synchronises)
   // setup call, not stream-ordered: every launch still queued on any stream (torch's pool streams are
   // non-blocking, so a plain hipMemcpy would not wait for them) finishes before the block changes
@@ -435,6 +437,7 @@ int as_set_quad_task(as_env_t* env, const as_quad_task_t* q) {
   }
   HIP_TRY(hipSetDevice(env->device));
   env->host.quad = *q;
+  as::fill_lane_table(env->host);
   // setup call, not stream-ordered: every launch still queued on any stream (torch's pool streams are
   // non-blocking, so a plain hipMemcpy would not wait for them) finishes before the block changes
   HIP_TRY(hipDeviceSynchronize());

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "../../include/allsteps.h"
+#include "allsteps_lane_table.h"
 
 namespace as {
 
@@ -37,7 +38,14 @@ struct Consts {
   // once the path is exhausted; fk_rounds = ceil(log2(max_path)) rounds cover every path
   uint32_t jump[kMaxLinks];
   int32_t fk_rounds;
+  // everything lane-indexed that k_step reads once per launch, one row per lane (allsteps_lane_table.h);
+  // rebuilt by fill_lane_table whenever the model, task or actuator fields above change
+  LaneRow lane[kLaneRows];
 };
+static_assert(kLaneRows == 32 && kMaxLinks <= kLaneRows && kMaxDofs <= kLaneRows, "one table row per k_step lane");
+inline void fill_lane_table(Consts& c) {
+  build_lane_table(c.lane, c.model, c.task, c.act, c.nv, c.lpath, c.lsub, c.ancmask, c.dsub, c.jump);
+}
 
 struct StepArgs {
   const Consts* consts;

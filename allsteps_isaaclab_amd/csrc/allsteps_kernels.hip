@@ -98,6 +98,9 @@ union alignas(16) PhaseScratch {
 // The constants block is read-only for the whole launch: address space 4 (constant) lets uniform
 // loads become scalar loads and keeps lane-varying ones global (not flat) loads.
 using CK = const __attribute__((address_space(4))) Consts;
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef const __attribute__((address_space(4))) u32x4 ConstV4;  // a 16-B chunk of a LaneRow
+typedef const uint32_t __attribute__((may_alias)) StateWord;     // a state word of any 4-B type
 
 // Per-lane tree plan and joint constants, read once per launch and kept in registers
 // (lane = link for the l* fields, lane = dof for the d* fields, lane = hinge for lo / hi).
@@ -157,7 +160,14 @@ struct EnvS {
   uint32_t mask[4];     // contact sensors 0..3 (2, 3: a quadruped's hind feet)
   int ndrop;            // contacts cut by the row budget over this launch's substeps (counters[kCntDropped])
   int nrows;            // constraint rows over this launch's substeps (the next launch's placement cost)
+  // the task epilogue's per-env words (kPk*: its scalars, then the nine stored body positions a launch
+  // without physics starts from), loaded with the rest of the state at launch start and parked here
+  // across the substeps: registers cannot hold them, and read after the final FK they were eleven
+  // exposed memory round trips
+  uint32_t pk[20];
 };
+enum { kPkIdx = 0, kPkPrev, kPkNext, kPkCount, kPkSwing, kPkEpLen, kPkPot, kPkOldPot, kPkFc0, kPkFc1, kPkEpisode,
+       kPkBody, kPkWords = kPkBody + 9 };
 
 struct Smem {
   EnvS env[EPB];
@@ -308,6 +318,7 @@ struct Stamp {
       if (threadIdx.x < kNumStamps) acc[threadIdx.x] = 0ull;
       t = t0 = __builtin_amdgcn_s_memtime();
       rt0 = __builtin_amdgcn_s_memrealtime();
+      __syncthreads();  // here, not in k_step: an untimed launch has no fence ahead of its first loads
     }
   }
   __device__ void count(int nrow, int nc) {
@@ -424,9 +435,10 @@ __device__ __forceinline__ LinkC load_link(const Consts& K, int lane) {
   return c;
 }
 
-template <bool kDyn>
-__device__ __forceinline__ void fk(const Consts& K, EnvS& s, int lane, const Topo& tp, LinkC lc, int max_path) {
-  const as_model_t& m = K.model;
+// KT: Consts in the generic or the constant address space (k_step's final FKs: uniform scalar loads).
+template <bool kDyn, class KT>
+__device__ __forceinline__ void fk(KT& K, EnvS& s, int lane, const Topo& tp, LinkC lc, int max_path) {
+  auto& m = K.model;
   const int nl = m.num_links;
   DynScratch& d = s.x.d;
   // opaque per call: nothing derived from them is hoisted out of the substep loop
@@ -497,7 +509,7 @@ __device__ __forceinline__ void fk(const Consts& K, EnvS& s, int lane, const Top
     for (int k = 0; k < 9; ++k) s.R[lane][k] = R[k];
 #pragma unroll
     for (int k = 0; k < 3; ++k) s.p[lane][k] = p[k];
-    if (kDyn) {
+    if constexpr (kDyn) {
       const int i = lane;
       float cw[3];
       matvec3(R, m.com[i], cw);
@@ -534,13 +546,15 @@ __device__ __forceinline__ void fk(const Consts& K, EnvS& s, int lane, const Top
       }
     }
   }
-  if (kDyn && lane == kZeroRow) {  // the walks' +0 rows (see take_bit_z)
+  if constexpr (kDyn) {
+    if (lane == kZeroRow) {  // the walks' +0 rows (see take_bit_z)
 #pragma unroll
-    for (int k = 0; k < 10; ++k) d.Ib[kZeroRow][k] = 0.f;
+      for (int k = 0; k < 10; ++k) d.Ib[kZeroRow][k] = 0.f;
 #pragma unroll
-    for (int k = 0; k < 6; ++k) d.Sq[kZeroRow][k] = 0.f;
+      for (int k = 0; k < 6; ++k) d.Sq[kZeroRow][k] = 0.f;
+    }
   }
-  if (kDyn) {
+  if constexpr (kDyn) {
     // root columns need the root COM c0 = R0 com_0 (p_0 = 0): every lane forms it itself
     float c0[3];
     matvec3(R0, m.com[0], c0);
@@ -984,35 +998,14 @@ __device__ void emit_contact(EnvS& s, int slot, int ncap, int link, int link2, i
   for (int k = 0; k < 3; ++k) { s.cn[slot][k] = n[k]; s.cpt[slot][k] = P[k] - n[k] * r; }
 }
 
-// Per-lane constants read from the constants block once per launch and kept in registers across the
-// substeps (lane-varying global loads every substep were an L2 round trip at the head of collide and
-// of the H rows): the geom of lane g, and the H-row masks of dof lane j.
+// Per-lane constants read from the lane table (allsteps_lane_table.h) once per launch and kept in
+// registers across the substeps (lane-varying global loads every substep were an L2 round trip at the
+// head of collide and of the H rows): the geom of lane g, and the H-row masks of dof lane j.
 struct GeomC {
   int link, type, foot;
   float r, p0[3], p1[3];
   uint32_t anc;  // h_row: dofs on the path of dof j's link
 };
-__device__ __forceinline__ GeomC load_geom(const Consts& K, int lane) {
-  const as_model_t& m = K.model;
-  const int g = lane < m.num_geoms ? lane : 0;
-  GeomC c;
-  c.link = m.geom_link[g];
-  c.type = m.geom_type[g];
-  c.foot = m.geom_foot[g];
-  c.r = m.geom_radius[g];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    c.p0[k] = m.geom_p0[g][k];
-    c.p1[k] = m.geom_p1[g][k];
-  }
-  const int j = lane < K.nv ? lane : 0;
-  c.anc = K.ancmask[j < 6 ? 0 : j - 5];
-  // opaque: the values are not rematerialised from memory inside the substep loop
-  asm volatile("" : "+v"(c.link), "+v"(c.type), "+v"(c.foot), "+v"(c.r), "+v"(c.anc));
-  asm volatile("" : "+v"(c.p0[0]), "+v"(c.p0[1]), "+v"(c.p0[2]), "+v"(c.p1[0]), "+v"(c.p1[1]), "+v"(c.p1[2]));
-  return c;
-}
-
 // as_capsule_contact (include/as_detmath.h) without branches: every lane forms the three quotients of
 // the main path (s, then t, then the clamped-end s) and selects; the degenerate cases (a sphere: a or e
 // <= eps) reuse the same quotients with their own numerators.  The values selected are the same
@@ -1895,11 +1888,12 @@ struct Useful {
 
 // allsteps_env.py:418-457 foot-state tick + 459-467 targets + 407-416 potentials (one env, serial).
 // dist_s is the swing foot's distance with the swing leg AFTER the tick (allsteps_env.py:371).
-__device__ void compute_useful(const Consts& K, const float* root_pos, const float* root_quat, const float* bp,
+// TaskT: as_task_t in the generic or the constant address space (k_step: uniform scalar loads)
+template <class TaskT>
+__device__ void compute_useful(TaskT& T, const float* root_pos, const float* root_quat, const float* bp,
                                const float* stones_env, int stride, uint32_t mask_r, uint32_t mask_l, int& idx,
                                int& prev, int& next, int& count, int& swing, float& pot, float& old_pot,
                                float* foot_contact, bool tick, Useful& u) {
-  const as_task_t& T = K.task;
   const int N = T.num_steps;
   float lower = fminf(bp[8], bp[5]);   // minimum(left_z, right_z)
   u.h = bp[2] - lower;
@@ -1957,97 +1951,145 @@ __global__ __launch_bounds__(kStepThreads) __attribute__((amdgpu_waves_per_eu(2,
   __shared__ Smem sm;
   // model / plan constants stay in global memory (5.7 KB, L1/K$-resident): LDS is the occupancy
   // budget, see EnvS
-  const Consts& K = *(const Consts*)(CK*)P.consts;
+  CK* Kc = (CK*)P.consts;
+  const Consts& K = *(const Consts*)Kc;
   const int el = threadIdx.x >> 5, lane = threadIdx.x & 31;
   const int n = P.n;
-  const int e_raw = P.wave_map ? P.wave_map[EPB * blockIdx.x + el] : xcd_block(blockIdx.x, gridDim.x) * EPB + el;
-  const bool valid = e_raw < n;
-  const int e = valid ? e_raw : n - 1;
   EnvS& s = sm.env[el];
   const as_state_t& st = P.st;
   Stamp ts{P.stamps, sm.stamp_acc, 0ull};
   ts.start();
+  // ---- load, batch 1: everything whose address is known at launch start, issued together -- the env
+  //      of this half, this lane's table row (allsteps_lane_table.h), the curriculum level and both
+  //      curriculum tables (lane c < 10 reads entry c; the level then picks a lane, not an address)
+  int e_raw = xcd_block(blockIdx.x, gridDim.x) * EPB + el;
+  if (P.wave_map) e_raw = P.wave_map[EPB * blockIdx.x + el];
+  const ConstV4* rowp = (const ConstV4*)&Kc->lane[lane];
+  u32x4 rc[kLaneChunks];
+#pragma unroll
+  for (int k = 0; k < kLaneChunks; ++k) rc[k] = rowp[k];
+  const int cur = *(const __attribute__((address_space(4))) int32_t*)st.curriculum;
+  const float cur_gain = Kc->task.gain_curriculum[lane < 10 ? lane : 0];
+  const float cur_term = Kc->task.term_curriculum[lane < 10 ? lane : 0];
+  const bool valid = e_raw < n;
+  const int e = valid ? e_raw : n - 1;
   // Under the wave map the second half of the grid holds the predicted-light waves, each the SIMD
   // partner of a heavy one.  The light wave starts with issue priority, until the first substep's row
   // count sets the rule below: with the heavy wave ahead from the first instruction the light partner
   // finished last (a wave's cycles grow more with its partner's rows than with its own, r06j), and
   // light-first for the opening phases only (not every substep's, nor the first two) measured best (r06k).
   if (P.wave_map && blockIdx.x >= (gridDim.x >> 1)) __builtin_amdgcn_s_setprio(1);
-  __syncthreads();
-  const as_model_t& m = K.model;
+  const __attribute__((address_space(4))) as_model_t& m = Kc->model;
   const int nh = m.num_hinges;
-  const as_task_t& T = K.task;
-  if (el == 0) sm.topo[lane] = load_topo(K, lane);
-  const Topo& tp = sm.topo[lane];
-  // ---- load
-  if (lane < 3) {
-    s.root_pos[lane] = st.root_pos[lane * n + e];
-    s.u[lane] = st.root_lin[lane * n + e];
-    s.u[3 + lane] = st.root_ang[lane * n + e];
-  }
-  if (lane < 4) s.root_quat[lane] = st.root_quat[lane * n + e];
-  if (lane == 0) { s.ndrop = 0; s.nrows = 0; }
-  const int cur = st.curriculum[0];
-  const float gain = T.gain_curriculum[cur];
-  if (lane < nh) {
-    int i = m.cfg_dof_link[lane] - 1;
-    s.qi[i] = st.q[lane * n + e];
-    s.u[6 + i] = st.qd[lane * n + e];
-    float a = 0.f;
-    if (P.mode != kModeReset) a = P.actions[(size_t)e * nh + lane];
-    a = fminf(fmaxf(a, -1.f), 1.f);                      // allsteps_env.py:267-268
-    s.act[lane] = a;
-    s.tau[i] = gain * m.gear[lane] * a;                  // allsteps_env.py:273
-    s.qt[i] = K.act.action_scale * a + K.act.default_q[lane];  // AS_ACT_DC_MOTOR (anymal_c_env.py:73-74)
-  }
-  for (int k = lane; k < 3 * T.num_steps; k += G) s.stones[k] = st.stones[k * n + e];
+  const __attribute__((address_space(4))) as_task_t& T = Kc->task;
+  // ---- load, batch 2: every per-env word of the launch, the task epilogue's included, behind one
+  //      wait.  The loads are unconditional at clamped rows (a lane past a field re-reads a row of the
+  //      same field) so that no branch, with a wait of its own, separates them; lane t < kPkWords
+  //      fetches epilogue word t.
+  const int l3 = lane < 3 ? lane : 0, l4 = lane < 4 ? lane : 0, lh = lane < nh ? lane : 0;
+  const int ns3 = 3 * T.num_steps;
+  const int k0 = lane < ns3 ? lane : 0, k1 = lane + G < ns3 ? lane + G : 0;
+  const float v_rp = st.root_pos[l3 * n + e], v_rl = st.root_lin[l3 * n + e], v_ra = st.root_ang[l3 * n + e];
+  const float v_rq = st.root_quat[l4 * n + e];
+  const float v_q = st.q[lh * n + e], v_qd = st.qd[lh * n + e];
+  // (a reset launch has no actions: it reads q at the same offset, in bounds, and drops the value)
+  const float* actp = P.mode != kModeReset ? P.actions : st.q;
+  float v_a = actp[(size_t)e * nh + lh];
+  if (P.mode == kModeReset) v_a = 0.f;
+  const float v_s0 = st.stones[k0 * n + e], v_s1 = st.stones[k1 * n + e];
   uint32_t mask[4] = {st.contact_mask[e], st.contact_mask[n + e], 0u, 0u};
+  uint32_t v_pk;
+  {
+    const void* const fp[kPkBody] = {st.idx, st.prev, st.next, st.count, st.swing, st.ep_len,
+                                     st.pot, st.old_pot, st.foot_contact, st.foot_contact, st.episode};
+    const void* pp = fp[0];
+#pragma unroll
+    for (int k = 1; k < kPkBody; ++k) pp = lane == k ? fp[k] : pp;
+    const bool body = lane >= kPkBody && lane < kPkWords;
+    pp = body ? st.body_pos : pp;
+    v_pk = ((StateWord*)pp)[lane == kPkFc1 ? n + e : (body ? (lane - kPkBody) * n + e : e)];
+  }
+  // the table row: tree plan (shared by both envs through LDS), joint, geom and H-row constants
+  Topo tp0;
+  tp0.lpath = rc[0].x; tp0.lsub = rc[0].y; tp0.dsub = rc[0].z; tp0.jump = rc[0].w;
+  tp0.lo = __uint_as_float(rc[1].x); tp0.hi = __uint_as_float(rc[1].y); tp0.arm = __uint_as_float(rc[1].z);
+  if (el == 0) sm.topo[lane] = tp0;
+  const Topo& tp = sm.topo[lane];
+  LinkC lc;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) lc.oq[k] = __uint_as_float(rc[2][k]);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    lc.ax[k] = __uint_as_float(rc[3 + k / 4][k % 4]);
+    lc.an[k] = __uint_as_float(rc[3 + (3 + k) / 4][(3 + k) % 4]);
+    lc.op[k] = __uint_as_float(rc[3 + (6 + k) / 4][(6 + k) % 4]);
+  }
+  const float row_gear = __uint_as_float(rc[5].y), row_dq = __uint_as_float(rc[5].z);
+  GeomC gc;
+  gc.link = (int)rc[6].x; gc.type = (int)rc[6].y; gc.foot = (int)rc[6].z; gc.r = __uint_as_float(rc[6].w);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    gc.p0[k] = __uint_as_float(rc[7][k]);
+    gc.p1[k] = __uint_as_float(rc[7 + (3 + k) / 4][(3 + k) % 4]);
+  }
+  gc.anc = rc[1].w;
+  // opaque: the values are not rematerialised from memory inside the substep loop
+  asm volatile("" : "+v"(gc.link), "+v"(gc.type), "+v"(gc.foot), "+v"(gc.r), "+v"(gc.anc));
+  asm volatile("" : "+v"(gc.p0[0]), "+v"(gc.p0[1]), "+v"(gc.p0[2]), "+v"(gc.p1[0]), "+v"(gc.p1[1]), "+v"(gc.p1[2]));
+  const float gain = readlane_f(cur_gain, cur);
+  const float term_h = readlane_f(cur_term, cur);  // allsteps_env.py:401, for the epilogue
+  if (lane < 3) {
+    s.root_pos[lane] = v_rp;
+    s.u[lane] = v_rl;
+    s.u[3 + lane] = v_ra;
+  }
+  if (lane < 4) s.root_quat[lane] = v_rq;
+  if (lane == 0) { s.ndrop = 0; s.nrows = 0; }
+  if (lane < nh) {
+    int i = (int)rc[9].w - 1;
+    s.qi[i] = v_q;
+    s.u[6 + i] = v_qd;
+    float a = fminf(fmaxf(v_a, -1.f), 1.f);              // allsteps_env.py:267-268
+    s.act[lane] = a;
+    s.tau[i] = gain * row_gear * a;                      // allsteps_env.py:273
+    s.qt[i] = Kc->act.action_scale * a + row_dq;         // AS_ACT_DC_MOTOR (anymal_c_env.py:73-74)
+  }
+  if (lane < ns3) s.stones[lane] = v_s0;
+  if (lane + G < ns3) s.stones[lane + G] = v_s1;
+  if (lane < kPkWords) s.pk[lane] = v_pk;
   __syncthreads();
   ts.mark(kStLoad);
   const bool do_physics = P.mode == kModeStep || P.mode == kModePhysics;
-  const LinkC lc = load_link(K, lane);
   // ---- physics
   if (do_physics) {
-    const GeomC gc = load_geom(K, lane);
-    for (int sub = 0; sub < K.sim.substeps; ++sub) substep<NV, SKIP>(K, sm, s, lane, tp, gc, lc, mask, ts);
+    const int substeps = Kc->sim.substeps;  // (through the generic reference it was re-read every substep)
+    for (int sub = 0; sub < substeps; ++sub) substep<NV, SKIP>(K, sm, s, lane, tp, gc, lc, mask, ts);
   }
   // This lane's reset constants (joint `lane` in cfg order: its link and limits, the start pose plain and
   // mirrored), loaded ahead of the final FK so that their global loads (L2 round trips) run under it
   // instead of heading the reset (the memory clobber keeps them there, not sunk into the reset
-  // branch); the limits then come from the tree plan in LDS.  The task's reward and the observation
-  // use the same link and limits.
-  int rs_li = 1, rs_src = lane;
-  float rs_q = 0.f, rs_qm = 0.f, rs_sg = 1.f, rs_lo = 0.f, rs_hi = 0.f;
-  {
-    // the mirror map through the constant address space (uniform: scalar loads, all issued together),
-    // applied by selects in the reference's order (the later match wins, as the sequential ifs)
-    const __attribute__((address_space(4))) as_task_t* Tc = &((CK*)P.consts)->task;
-    int rmap[9], lmap[9];
-#pragma unroll
-    for (int t = 0; t < 9; ++t) { rmap[t] = Tc->right_idx[t]; lmap[t] = Tc->left_idx[t]; }
-    const int ng0 = Tc->neg_idx[0], ng1 = Tc->neg_idx[1];
-#pragma unroll
-    for (int t = 0; t < 9; ++t) {
-      rs_src = rmap[t] == lane ? lmap[t] : rs_src;
-      rs_src = lmap[t] == lane ? rmap[t] : rs_src;
-    }
-    rs_sg = ng0 == lane || ng1 == lane ? -1.f : 1.f;
-    if (lane < nh) {
-      rs_q = T.init_q[lane] * 1.f;
-      rs_qm = T.init_q[rs_src] * rs_sg;
-      rs_li = m.cfg_dof_link[lane];
-    }
+  // branch).  The task's reward and the observation use the same link and limits.
+  // (the two reset chunks of the table row, allsteps_lane_table.h: the mirror map is resolved there;
+  // lanes past the hinges get link 1 and zeros.)  The optional reset draws are the only other global
+  // loads after the substeps, issued here as well.
+  // (through the generic pointer: loads from the constant address space are invariant, and the clobber
+  // below would not hold them here)
+  const u32x4* rowg = (const u32x4*)&K.lane[lane];
+  const u32x4 rr8 = rowg[8], rr9 = rowg[9];
+  const float rs_q = __uint_as_float(rr8.z), rs_qm = __uint_as_float(rr8.w), rs_sg = __uint_as_float(rr9.x);
+  const float rs_lo = __uint_as_float(rr9.y), rs_hi = __uint_as_float(rr9.z);
+  const int rs_li = (int)rr9.w;
+  float rd_m = 0.f, rd_n = 0.f;  // mirror draw, this lane's joint-noise draw
+  if (P.reset_draws && P.mode != kModePhysics) {
+    rd_m = P.reset_draws[(size_t)e * 22];
+    rd_n = P.reset_draws[(size_t)e * 22 + 1 + lh];
   }
   asm volatile("" ::: "memory");
   if (do_physics) {
-    fk<false>(K, s, lane, tp, lc, K.max_path);  // FK of the final pose for body_pos_w (articulation_data.py:439)
+    fk<false>(*Kc, s, lane, tp, lc, Kc->max_path);  // FK of the final pose for body_pos_w (articulation_data.py:439)
     if (lane == 0) { s.mask[0] = mask[0]; s.mask[1] = mask[1]; s.mask[2] = mask[2]; s.mask[3] = mask[3]; }
   }
   ts.mark(kStFKFinal);
-  if (lane < nh) {  // m.lower / upper[li] as copied into the tree plan (Topo: hinge li - 1 is link li)
-    rs_lo = sm.topo[rs_li - 1].lo;
-    rs_hi = sm.topo[rs_li - 1].hi;
-  }
   if (lane == 0 && !do_physics) { s.mask[0] = mask[0]; s.mask[1] = mask[1]; }
   __syncthreads();
   float bp[9];
@@ -2056,19 +2098,19 @@ __global__ __launch_bounds__(kStepThreads) __attribute__((amdgpu_waves_per_eu(2,
     for (int b = 0; b < 3; ++b)
       for (int k = 0; k < 3; ++k) bp[3 * b + k] = s.root_pos[k] + s.p[ls[b]][k];
   } else {
-    for (int k = 0; k < 9; ++k) bp[k] = st.body_pos[k * n + e];
+    for (int k = 0; k < 9; ++k) bp[k] = __uint_as_float(s.pk[kPkBody + k]);
   }
-  // ---- task epilogue (direct_rl_env.py:349-364)
-  int idx = st.idx[e], prev = st.prev[e], next = st.next[e], count = st.count[e], swing = st.swing[e];
-  int ep_len = st.ep_len[e];
-  float pot = st.pot[e], old_pot = st.old_pot[e];
-  float fc[2] = {st.foot_contact[e], st.foot_contact[n + e]};
-  uint32_t episode = st.episode[e];
+  // ---- task epilogue (direct_rl_env.py:349-364), on the scalars parked at launch start
+  int idx = (int)s.pk[kPkIdx], prev = (int)s.pk[kPkPrev], next = (int)s.pk[kPkNext], count = (int)s.pk[kPkCount];
+  int swing = (int)s.pk[kPkSwing], ep_len = (int)s.pk[kPkEpLen];
+  float pot = __uint_as_float(s.pk[kPkPot]), old_pot = __uint_as_float(s.pk[kPkOldPot]);
+  float fc[2] = {__uint_as_float(s.pk[kPkFc0]), __uint_as_float(s.pk[kPkFc1])};
+  uint32_t episode = s.pk[kPkEpisode];
   bool done = false;
   if (P.mode == kModeStep || P.mode == kModeTask) {
     ep_len += 1;                                         // direct_rl_env.py:351
     Useful u;
-    compute_useful(K, s.root_pos, s.root_quat, bp, s.stones, 1, s.mask[0], s.mask[1], idx, prev, next, count,
+    compute_useful(T, s.root_pos, s.root_quat, bp, s.stones, 1, s.mask[0], s.mask[1], idx, prev, next, count,
                    swing, pot, old_pot, fc, true, u);    // allsteps_env.py:397 tick #1
     // lane-parallel pieces of the reward: sum a^2, sum |qd a|, #(|q_scaled| > 0.99)
     float a2 = 0.f, en = 0.f;
@@ -2087,7 +2129,7 @@ __global__ __launch_bounds__(kStepThreads) __attribute__((amdgpu_waves_per_eu(2,
     const float* lv = s.u;
     float speed = sqrtf(lv[0] * lv[0] + lv[1] * lv[1] + lv[2] * lv[2]);
     bool time_out = ep_len >= T.max_episode_length - 1;  // allsteps_env.py:399
-    bool fell = u.h < T.term_curriculum[cur];            // :401
+    bool fell = u.h < term_h;                             // :401
     bool so_fast = speed > 5.0f;                         // :402
     bool died = s.root_pos[2] < T.fall_abs;              // :403
     bool terminated = fell || so_fast || died;
@@ -2137,7 +2179,7 @@ __global__ __launch_bounds__(kStepThreads) __attribute__((amdgpu_waves_per_eu(2,
       atomicAdd(&P.counters[kCntStride * (1 + (int)(blockIdx.x % kCntSlots))], wsum);
       if (wdrop) atomicAdd(&P.counters[kCntDropped], wdrop);
       if (wdone) P.counters[0] = 1;
-      if (T.regen_footsteps) P.counters[kCntLevel] = P.st.curriculum[0];  // same value from every wave
+      if (T.regen_footsteps) P.counters[kCntLevel] = cur;  // same value from every wave
     }
   }
   ts.mark(kStTask);
@@ -2148,11 +2190,8 @@ __global__ __launch_bounds__(kStepThreads) __attribute__((amdgpu_waves_per_eu(2,
   const bool regen = T.regen_footsteps && P.mode != kModePhysics && done && idx > T.num_steps / 2;
   if (P.mode != kModePhysics && any_done) {
     if (done) {
-      float dm = 0.f, dn = 0.f;  // mirror draw, this lane's joint-noise draw
-      if (P.reset_draws) {
-        dm = P.reset_draws[(size_t)e * 22];
-        if (lane < nh) dn = P.reset_draws[(size_t)e * 22 + 1 + lane];
-      } else {
+      float dm = rd_m, dn = rd_n;  // the caller's draws (loaded ahead of the final FK), or Philox
+      if (!P.reset_draws) {
         float blk[4];
         philox_block(P.seed, (uint32_t)(P.env_offset + e), episode, 0u, kResetTag, blk);
         dm = blk[0];
@@ -2180,7 +2219,8 @@ __global__ __launch_bounds__(kStepThreads) __attribute__((amdgpu_waves_per_eu(2,
         s.u[6 + li - 1] = jv;
       }
       if (lane < 3) {
-        s.root_pos[lane] = T.init_root[lane];
+        const float ir[3] = {T.init_root[0], T.init_root[1], T.init_root[2]};  // uniform: scalar loads
+        s.root_pos[lane] = lane == 0 ? ir[0] : (lane == 1 ? ir[1] : ir[2]);
         s.u[lane] = 0.f;
         s.u[3 + lane] = 0.f;
       }
@@ -2194,7 +2234,7 @@ __global__ __launch_bounds__(kStepThreads) __attribute__((amdgpu_waves_per_eu(2,
       episode += 1u;
     }
     __syncthreads();
-    fk<false>(K, s, lane, tp, lc, K.max_path);  // body_pos of the reset pose (write_joint_state_to_sim invalidates FK)
+    fk<false>(*Kc, s, lane, tp, lc, Kc->max_path);  // body_pos of the reset pose (write_joint_state_to_sim invalidates FK)
     if (done) {
       const int ls[3] = {m.torso_link, m.foot_link[0], m.foot_link[1]};
       for (int b = 0; b < 3; ++b)
@@ -2211,7 +2251,7 @@ __global__ __launch_bounds__(kStepThreads) __attribute__((amdgpu_waves_per_eu(2,
     int i2 = idx, p2 = prev, n2 = next, c2 = count, w2 = swing;
     float pot2 = pot, op2 = old_pot, fc2[2] = {fc[0], fc[1]};
     Useful u2;
-    compute_useful(K, s.root_pos, s.root_quat, bp, s.stones, 1, s.mask[0], s.mask[1], i2, p2, n2, c2, w2, pot2,
+    compute_useful(T, s.root_pos, s.root_quat, bp, s.stones, 1, s.mask[0], s.mask[1], i2, p2, n2, c2, w2, pot2,
                    op2, fc2, true, u2);
     float* ob = s.x.obs;
     uint32_t* side = P.side;
