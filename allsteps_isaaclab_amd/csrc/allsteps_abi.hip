@@ -207,6 +207,14 @@ int as_create(int32_t num_envs, const as_model_t* model, const as_sim_t* sim, co
   if (!as::step_supported_nv(h.nv))
     return fail(AS_ERR_INVALID, "as_create: no k_step instantiation for " + std::to_string(h.nv) + " dofs");
   as::fill_lane_table(h);
+  // collide pass B tests a stone pair on a group of up to 2^4 lanes (results are the same at any level);
+  // ALLSTEPS_PAIR_GROUP=1..4 caps the level, 1 = one lane per pair throughout (tests, A/B timing)
+  h.pair_group_cap = 4;
+  if (const char* pg = std::getenv("ALLSTEPS_PAIR_GROUP")) {
+    if (std::strlen(pg) != 1 || pg[0] < '1' || pg[0] > '4')
+      return fail(AS_ERR_INVALID, std::string("as_create: ALLSTEPS_PAIR_GROUP=") + pg + ", expected 1, 2, 3 or 4");
+    h.pair_group_cap = pg[0] - '0';
+  }
 
   as_env* env = new as_env();
   env->n = num_envs;

@@ -6,6 +6,7 @@
 
 #include "../../include/allsteps.h"
 #include "allsteps_lane_table.h"
+#include "allsteps_pair_group.h"
 
 namespace as {
 
@@ -38,6 +39,9 @@ struct Consts {
   // once the path is exhausted; fk_rounds = ceil(log2(max_path)) rounds cover every path
   uint32_t jump[kMaxLinks];
   int32_t fk_rounds;
+  // collide pass B: the largest lane-group level per stone pair (allsteps_pair_group.h): 4, or what
+  // ALLSTEPS_PAIR_GROUP set at as_create (1: one lane per pair, always)
+  int32_t pair_group_cap;
   // everything lane-indexed that k_step reads once per launch, one row per lane (allsteps_lane_table.h);
   // rebuilt by fill_lane_table whenever the model, task or actuator fields above change
   LaneRow lane[kLaneRows];

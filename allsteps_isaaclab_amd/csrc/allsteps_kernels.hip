@@ -182,7 +182,8 @@ struct Smem {
 template <int CTRL>
 __device__ __forceinline__ float dpp(float v) {
   // bound_ctrl: the quad permutes and row mirrors used here never read outside the row, so the
-  // "old" operand is dead and the move folds into the consuming v_add_f32_dpp
+  // "old" operand is dead and the move folds into the consuming v_add_f32_dpp.  (collide's flush_grp also
+  // uses row shifts, which do read outside at a row's first lanes and get 0 there: it discards those lanes.)
   return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true));
 }
 
@@ -304,15 +305,19 @@ __device__ __forceinline__ void half_min_n(float (&v)[N]) {
 // atomic per phase boundary would put a contended memory round trip into the next phase.
 // With p[kWaveRecFlag] != 0 each wave also writes a record of its own (the last launch's waves:
 // phase cycles, total, start / end time, HW_ID / XCC_ID, rows and contacts summed over substeps per
-// env) at p + kWaveRecBase + block * kWaveRecWords, for tail analysis (scripts/stamps.py).
-constexpr int kWaveRecFlag = 31, kWaveRecBase = 64, kWaveRecWords = 26;
-static_assert(16 + kNumStamps <= kWaveRecFlag && kNumStamps + 11 <= kWaveRecWords, "stamp slots");
+// env; collide's pass B: the stone pairs of each env, their sum over the substeps in bits 0-15 and the
+// largest single flush's in bits 16-31 -- the substep's own count as long as that is at most
+// kPairsPerChunk, one flush per substep -- and the wave's flushes per group level, 8 bits each: one lane
+// per pair, then L = 2, 3, 4) at p + kWaveRecBase + block * kWaveRecWords, for tail analysis
+// (scripts/stamps.py; the record's size and words are part of as_debug_stamps' contract, include/allsteps.h).
+constexpr int kWaveRecFlag = 31, kWaveRecBase = 64, kWaveRecWords = 30;
+static_assert(16 + kNumStamps <= kWaveRecFlag && kNumStamps + 14 <= kWaveRecWords, "stamp slots");
 struct Stamp {
   unsigned long long* p;
   unsigned long long* acc;  // LDS, kNumStamps
   unsigned long long t;
   unsigned long long t0 = 0ull, rt0 = 0ull;  // s_memtime / s_memrealtime (100 MHz) at the start
-  unsigned rows = 0u, cons = 0u;
+  unsigned rows = 0u, cons = 0u, prs = 0u, lvls = 0u;
   __device__ void start() {
     if (p) {
       if (threadIdx.x < kNumStamps) acc[threadIdx.x] = 0ull;
@@ -325,6 +330,13 @@ struct Stamp {
     if (p) {
       rows += (unsigned)nrow;
       cons += (unsigned)nc;
+    }
+  }
+  __device__ void pairs(int np, int level) {  // one pass-B flush: this env's pairs, the wave's level (0, 2, 3, 4)
+    if (p) {
+      const unsigned mx = prs >> 16 > (unsigned)np ? prs >> 16 : (unsigned)np;
+      prs = ((prs + (unsigned)np) & 0xffffu) | (mx << 16);
+      lvls += 1u << (8 * (level < 2 ? 0 : level - 1));
     }
   }
   __device__ void mark(int k) {
@@ -353,8 +365,9 @@ struct Stamp {
           rec[kNumStamps + 9] = rt0; rec[kNumStamps + 10] = __builtin_amdgcn_s_memrealtime();
           rec[kNumStamps + 3] = hw; rec[kNumStamps + 4] = xcc;
           rec[kNumStamps + 5] = rows; rec[kNumStamps + 7] = cons;
+          rec[kNumStamps + 11] = prs; rec[kNumStamps + 13] = lvls;
         }
-        if (k == 32) { rec[kNumStamps + 6] = rows; rec[kNumStamps + 8] = cons; }
+        if (k == 32) { rec[kNumStamps + 6] = rows; rec[kNumStamps + 8] = cons; rec[kNumStamps + 12] = prs; }
       } else {
         if (threadIdx.x < kNumStamps) {
           atomicAdd(p + threadIdx.x, acc[threadIdx.x]);
@@ -1057,8 +1070,9 @@ __device__ __forceinline__ float capsule_contact_sel(const float* a1, const floa
 //   1. the priority geoms (the feet: geoms [0, num_priority_geoms)) against the candidate stones,
 //      stone-major, geom-minor;  2. every other geom against the candidate stones, likewise;
 //   3. robot self-contacts, one per self-collision pair in table order.
+// gcap: the largest pass-B group level (Consts::pair_group_cap); ts: the diagnostic pair / level counts.
 __device__ __forceinline__ int collide(const Consts& K, EnvS& s, int lane, int ncap, const GeomC& gc, const float* h,
-                                       float margin) {
+                                       float margin, int gcap, Stamp& ts) {
   const as_model_t& m = K.model;
   const int nst = K.task.num_steps, ng = m.num_geoms, npri = m.num_priority_geoms, nsp = m.num_self_pairs;
   // self-collision pair words of this lane (pairs lane, lane + 32, ...), loaded first so that their
@@ -1128,7 +1142,8 @@ __device__ __forceinline__ int collide(const Consts& K, EnvS& s, int lane, int n
   // flushes its partial list: chunk boundaries change neither the contacts nor their order, and one
   // flush for the wave replaces one per env under divergence), so the list never exceeds 32 + 22
   // entries; the search runs over every pair even past ncap contacts (the surplus is counted, not
-  // emitted).
+  // emitted).  When the wave's larger pending count is at most 8 -- nearly always: the last flush of a
+  // substep -- a pair gets a group of lanes instead of one (flush_grp below).
   {
     float* gs = s.x.col.g[lane];  // staging of this lane's geom for pass B and the self pairs
     if (gv) {
@@ -1215,6 +1230,73 @@ __device__ __forceinline__ int collide(const Consts& K, EnvS& s, int lane, int n
     pend = rest;
     __syncthreads();
   };
+  // Pass B with a group of 2^L lanes per pair (L = 2, 3, 4: pair p at lanes p << L, npairs <= 32 >> L),
+  // entered by the whole wave.  A flush above is one lane's serial instruction stream whatever the pair
+  // count, and a substep has 1.5 pairs on average; here the idle lanes take that stream
+  // apart.  Every value keeps its operations and operands, so the contacts are the same bits:
+  //  - the bisection runs L rounds at once (allsteps_pair_group.h): sub-lane k evaluates the slope at its
+  //    dyadic point, one ballot hands the group's signs to every lane, each lane walks the L decisions;
+  //  - sub-lanes 0, 1, 2 evaluate sd_box at A, at B and at P(t*): one instance in the stream, not three,
+  //    and each holds at most one contact.  Lane order within the half is then the emission order
+  //    (pair-major; t = 0, t = 1, t*), so the prefix count over lanes gives the slots and one
+  //    emit_contact per lane replaces the packing selects and three conditional calls.
+  // A sphere pair uses sub-lane 0 only.  L is a runtime value: one copy of the code for the three levels.
+  auto flush_grp = [&](int npairs, int L) {
+    const int gm = (1 << L) - 1, k = lane & gm, pi = lane >> L;
+    const bool act = pi < npairs;
+    const int e = act ? pl[pi] : 0;  // (a group without a pair runs on stone 0, geom 0 and emits nothing)
+    const int gi = e & 0xff, pst = e >> 8;
+    const float* gq = s.x.col.g[gi];
+    const float A[3] = {gq[0], gq[1], gq[2]}, Bb[3] = {gq[3], gq[4], gq[5]};
+    const float pr = gq[6];
+    const int meta = __float_as_int(gq[7]);
+    const int pty = meta & 15, pfoot = ((meta >> 4) & 15) - 1, plink = meta >> 8;
+    float c[3];
+    for (int i = 0; i < 3; ++i) c[i] = s.stones[3 * pst + i] - s.root_pos[i];
+    float lo = 0.f, d = 1.f;  // the interval [lo, lo + d]
+    const float sc = pair_group_scale(L);
+    const int g0 = (threadIdx.x & 63) & ~gm;  // the group's first lane in the wave
+#pragma unroll 1
+    for (int it = 0; it < kBisectIters; it += L) {
+      const float w = d * sc;
+      const bool up = sd_box_slope(A, Bb, pair_group_point(lo, w, k), c, h) > 0.f;
+      pair_group_walk(lo, w, L, (uint32_t)(__ballot(up) >> g0));  // reads the group's bits 0 .. 2^L - 2
+      d = w;
+    }
+    const float tm = 0.5f * (lo + (lo + d));
+    float Q[3], nq[3];
+    // (P(t*) formed by every lane, and the sub-lane's point picked by bit masks -- two v_bfi per
+    // coordinate: written as ?: the compiler turns each pick into exec-mask diamonds on k; the emission
+    // test below in bit operations for the same reason)
+    const uint32_t m0 = k == 0 ? ~0u : 0u, m1 = k == 1 ? ~0u : 0u;
+    for (int i = 0; i < 3; ++i) {
+      const uint32_t ps = __float_as_uint(A[i] + tm * (Bb[i] - A[i]));
+      const uint32_t b1 = (__float_as_uint(Bb[i]) & m1) | (ps & ~m1);
+      Q[i] = __uint_as_float((__float_as_uint(A[i]) & m0) | (b1 & ~m0));
+    }
+    const float sv = sd_box(Q, c, h, nq) - pr;
+    // sub-lane 2: min(s0, s1) from its two neighbours (row_shr:2, row_shr:1; a group never straddles a row).
+    // On sub-lanes 0 and 1 the shifts reach into the previous group, or past the row's start where
+    // bound_ctrl gives 0: smin is read on sub-lane 2 alone (sel below), the rest is discarded.
+    const float smin = fminf(dpp<0x112>(sv), dpp<0x111>(sv));
+    const bool cap = pty != 0;
+    const bool sel = (k == 0) | (cap & (k == 1)) | (cap & (k == 2) & (sv < smin - 0.002f));
+    const int cnt = (int)(act & (sv < margin) & sel);
+    int total;
+    const int slot = base + half_scan3(cnt, total);
+    if (cnt) emit_contact(s, slot, ncap, plink, -1, pst, pfoot, Q, nq, sv, pr);
+    base += total;
+    pend -= npairs;  // (the level was chosen to hold every pending pair: nothing to shift)
+    __syncthreads();
+  };
+  static_assert(kBisectIters == kPairGroupIters, "allsteps_pair_group.h: the group rounds cover kBisectIters");
+  // wave-uniform: the group level for the wave's larger pending count, and the flush that goes with it
+  auto flush_any = [&](int wpend) {
+    const int L = pair_group_level(wpend, gcap);
+    const int np = pend < kPairsPerChunk ? pend : kPairsPerChunk;
+    ts.pairs(np, L);
+    if (L) flush_grp(np, L); else flush(np);
+  };
   __syncthreads();
   // pass A (lane = geom): one bounding test per (candidate stone, geom), kept as a per-stone mask of
   // the surviving geoms; the masks then become the pair list class by class (feet first),
@@ -1237,19 +1319,25 @@ __device__ __forceinline__ int collide(const Consts& K, EnvS& s, int lane, int n
   __syncthreads();
   const uint32_t primask = npri >= 32 ? ~0u : (1u << npri) - 1u;
   const int wcand = max(__builtin_amdgcn_readlane(ncand, 0), __builtin_amdgcn_readlane(ncand, 32));
+  // Classes 0 and 1 append the pairs; "class" 2 is one empty round that appends nothing and flushes what is
+  // left, so that pass B has one call site (one copy of flush / flush_grp in the code) instead of a second
+  // one behind the loops.
 #pragma unroll 1
-  for (int cls = 0; cls < 2; ++cls) {
+  for (int cls = 0; cls < 3; ++cls) {
+    const int nci = cls < 2 ? wcand : 1;
 #pragma unroll 1
-    for (int ci = 0; ci < wcand; ++ci) {
-      const uint32_t bl = ci < ncand ? cneed[ci] & (cls == 0 ? primask : ~primask) : 0u;
+    for (int ci = 0; ci < nci; ++ci) {
+      const uint32_t bl = cls < 2 && ci < ncand ? cneed[ci] & (cls == 0 ? primask : ~primask) : 0u;
       if ((bl >> lane) & 1u) pl[pend + __popc(bl & ((1u << lane) - 1u))] = (s.cand[ci] << 8) | lane;
       pend += __popc(bl);  // no barrier: the single wave's LDS operations complete in issue order
       // wave-uniform flush decision (see above); the candidate loop runs to the wave's larger count
-      if (max(__builtin_amdgcn_readlane(pend, 0), __builtin_amdgcn_readlane(pend, 32)) >= kPairsPerChunk)
-        flush(pend < kPairsPerChunk ? pend : kPairsPerChunk);
+      const int wpend = max(__builtin_amdgcn_readlane(pend, 0), __builtin_amdgcn_readlane(pend, 32));
+      // while appending: a full chunk; in the closing round: whatever is pending (fewer than kPairsPerChunk
+      // in either env, since every full chunk was flushed as it filled: exactly one flush, of everything)
+      const bool appending = cls < 2;
+      if (appending ? wpend >= kPairsPerChunk : wpend > 0) flush_any(wpend);
     }
   }
-  if (pend > 0) flush(pend);
   // self-contacts.  (A) lane = pair: the bounding-sphere filter; the surviving pairs are appended to
   // the pending list in table order.  (B) lane = pending pair, in chunks of G: the capsule-capsule
   // closest points (capsule_contact_sel: as_detmath.h's as_capsule_contact, which the oracle runs, in
@@ -1636,8 +1724,10 @@ __device__ void substep(const Consts& K0, Smem& sm, EnvS& s, int lane0, const To
   const int ncap = (MAXR - nlim) / 3 < MAXC ? (MAXR - nlim) / 3 : MAXC;
   float sb = K.sim.baumgarte, ssl = K.sim.slop, smd = K.sim.max_depen_vel, sfr = K.sim.friction, smg = K.sim.margin;
   float sh[3] = {K.sim.stone_half[0], K.sim.stone_half[1], K.sim.stone_half[2]};
-  asm volatile("" : "+s"(sb), "+s"(ssl), "+s"(smd), "+s"(sfr), "+s"(smg), "+s"(sh[0]), "+s"(sh[1]), "+s"(sh[2]));
-  const int nc = collide(K, s, lane, ncap, gc, sh, smg);
+  int gcap = K.pair_group_cap;
+  asm volatile("" : "+s"(sb), "+s"(ssl), "+s"(smd), "+s"(sfr), "+s"(smg), "+s"(sh[0]), "+s"(sh[1]), "+s"(sh[2]),
+               "+s"(gcap));
+  const int nc = collide(K, s, lane, ncap, gc, sh, smg, gcap, ts);
   ts.mark(kStCollide);
 
   if (lane < nc) {  // contact rows 3c..3c+2: normal, tangent 1, tangent 2
@@ -1889,15 +1979,19 @@ struct Useful {
 // allsteps_env.py:418-457 foot-state tick + 459-467 targets + 407-416 potentials (one env, serial).
 // dist_s is the swing foot's distance with the swing leg AFTER the tick (allsteps_env.py:371).
 // TaskT: as_task_t in the generic or the constant address space (k_step: uniform scalar loads)
+// pose: u.h, u.roll and u.pitch are formed here; false (wave-uniform) when u already holds them for this
+// root_quat and bp (k_step's second tick in a wave where no env reset).
 template <class TaskT>
 __device__ void compute_useful(TaskT& T, const float* root_pos, const float* root_quat, const float* bp,
                                const float* stones_env, int stride, uint32_t mask_r, uint32_t mask_l, int& idx,
                                int& prev, int& next, int& count, int& swing, float& pot, float& old_pot,
-                               float* foot_contact, bool tick, Useful& u) {
+                               float* foot_contact, bool tick, Useful& u, bool pose = true) {
   const int N = T.num_steps;
-  float lower = fminf(bp[8], bp[5]);   // minimum(left_z, right_z)
-  u.h = bp[2] - lower;
-  euler_rp_from_quat(root_quat, &u.roll, &u.pitch);
+  if (pose) {
+    float lower = fminf(bp[8], bp[5]);   // minimum(left_z, right_z)
+    u.h = bp[2] - lower;
+    euler_rp_from_quat(root_quat, &u.roll, &u.pitch);
+  }
   u.reached = 0;
   u.dist_s = 0.f;
   if (tick) {
@@ -2107,9 +2201,9 @@ __global__ __launch_bounds__(kStepThreads) __attribute__((amdgpu_waves_per_eu(2,
   float fc[2] = {__uint_as_float(s.pk[kPkFc0]), __uint_as_float(s.pk[kPkFc1])};
   uint32_t episode = s.pk[kPkEpisode];
   bool done = false;
+  Useful u{};  // tick #1's; its h / roll / pitch serve tick #2 where the pose cannot have changed (below)
   if (P.mode == kModeStep || P.mode == kModeTask) {
     ep_len += 1;                                         // direct_rl_env.py:351
-    Useful u;
     compute_useful(T, s.root_pos, s.root_quat, bp, s.stones, 1, s.mask[0], s.mask[1], idx, prev, next, count,
                    swing, pot, old_pot, fc, true, u);    // allsteps_env.py:397 tick #1
     // lane-parallel pieces of the reward: sum a^2, sum |qd a|, #(|q_scaled| > 0.99)
@@ -2250,9 +2344,12 @@ __global__ __launch_bounds__(kStepThreads) __attribute__((amdgpu_waves_per_eu(2,
   if (P.obs) {
     int i2 = idx, p2 = prev, n2 = next, c2 = count, w2 = swing;
     float pot2 = pot, op2 = old_pot, fc2[2] = {fc[0], fc[1]};
-    Useful u2;
+    // h, roll and pitch depend on root_quat and bp alone, which only a reset changes between the ticks:
+    // a wave without a done env (wave-uniform; 94 % of them) keeps tick #1's instead of a second atan2 /
+    // asin / two rem2pi
+    Useful u2 = u;
     compute_useful(T, s.root_pos, s.root_quat, bp, s.stones, 1, s.mask[0], s.mask[1], i2, p2, n2, c2, w2, pot2,
-                   op2, fc2, true, u2);
+                   op2, fc2, true, u2, any_done || !(P.mode == kModeStep || P.mode == kModeTask));
     float* ob = s.x.obs;
     uint32_t* side = P.side;
     if (lane == 0) {

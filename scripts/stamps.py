@@ -23,7 +23,7 @@ from allsteps_isaaclab_amd.envs.allsteps_env_cfg import AllstepsEnvCfg  # noqa: 
 PHASES = ["load", "fk", "rnea", "hrow", "sweep", "solve", "collide", "rows", "wsolve", "pgs", "integrate", "fkfinal",
           "task", "reset", "store"]
 NP = len(PHASES)
-BASE, WORDS = 64, 26
+BASE, WORDS = 64, 30
 
 
 def simd_key(r):
@@ -66,6 +66,25 @@ def wave_records(env, acts) -> np.ndarray:
     return np.stack(recs)
 
 
+def pair_summary(R) -> dict:
+    """collide's pass B from the records (words NP + 11 .. NP + 13): per env and launch the stone pairs summed
+    over the substeps (bits 0-15) and the largest single flush (bits 16-31: the largest substep's count as long
+    as no substep has more than 32 pairs, since a substep is then one flush); per wave the flushes at each group
+    level (8 bits each: one lane per pair, L = 2, 3, 4)."""
+    pr = np.concatenate([R[:, :, NP + 11].ravel(), R[:, :, NP + 12].ravel()])
+    mx = pr >> 16
+    lv = R[:, :, NP + 13]
+    fl = np.array([int(((lv >> (8 * i)) & 0xff).sum()) for i in range(4)])
+    waves = R.shape[0] * R.shape[1]
+    return {"pairs_per_env_launch_mean": round(float((pr & 0xffff).mean()), 3),
+            "max_pairs_in_a_flush": {"hist": np.bincount(np.minimum(mx, 33), minlength=34).tolist(),
+                                       "p50": int(np.percentile(mx, 50)), "p90": int(np.percentile(mx, 90)),
+                                       "p99": int(np.percentile(mx, 99)), "max": int(mx.max())},
+            "flushes_per_wave_launch": round(float(fl.sum()) / waves, 3),
+            "flush_share_by_level": {k: round(float(v) / max(int(fl.sum()), 1), 4)
+                                     for k, v in zip(("one_lane", "L2", "L3", "L4"), fl)}}
+
+
 def latency_summary(R) -> dict:
     """Latency-side figures of k_step (bench.py roofline.latency): per-wave cycles (mean, slowest),
     the launch's span in cycles (first wave start to last wave end), the mean / slowest wave's share
@@ -84,6 +103,9 @@ def latency_summary(R) -> dict:
             "critical_path_phases": {PHASES[k]: int(R[worst, i, k]) for k in range(NP)},
             "critical_path_rows": [int(R[worst, i, NP + 5]), int(R[worst, i, NP + 6])],
             "mean_phases": {PHASES[k]: int(R[:, :, k].mean()) for k in range(NP)},
+            "critical_path_pass_b": {"pairs": [int(R[worst, i, NP + 11] & 0xffff), int(R[worst, i, NP + 12] & 0xffff)],
+                                     "flushes_by_level": [int((R[worst, i, NP + 13] >> (8 * k)) & 0xff) for k in range(4)]},
+            "pass_b": pair_summary(R),
             "launches": int(R.shape[0])}
 
 
