@@ -94,147 +94,26 @@ const char* as_last_error(void) { return g_err.c_str(); }
 
 int as_sweep_plan(const as_model_t* model, uint64_t* skip_mask) {
   if (!model) return fail(AS_ERR_INVALID, "as_sweep_plan: null model");
+  std::string err;
+  // no state here: foot ids 2 and 3 pass, as_create checks them against the state it is given
+  if (!as::check_model(*model, true, err) || !as::check_parents(*model, err))
+    return fail(AS_ERR_INVALID, "as_sweep_plan: " + err);
   const int nv = 6 + model->num_hinges;
-  if (!as::step_supported_nv(nv) || model->num_links < 1 || model->num_links > as::kMaxLinks)
-    return fail(AS_ERR_INVALID, "as_sweep_plan: no k_step instantiation for this model");
-  for (int i = 1; i < model->num_links; ++i)
-    if (model->parent[i] < 0 || model->parent[i] >= i) return fail(AS_ERR_INVALID, "as_sweep_plan: parent not topological");
+  if (!as::step_supported_nv(nv)) return fail(AS_ERR_INVALID, "as_sweep_plan: no k_step instantiation for this model");
   const uint64_t valid = as::sweep_skip_mask(*model);
   const uint64_t compiled = nv == 27 ? as::kSweepSkip27 : as::kSweepSkip18;
   if (skip_mask) *skip_mask = valid;
   return (compiled & ~valid) == 0ull ? 1 : 0;
 }
 
-int as_create(int32_t num_envs, const as_model_t* model, const as_sim_t* sim, const as_task_t* task,
-              const as_state_t* state, uint64_t seed, int32_t device, int64_t env_id_offset, as_env_t** out) {
-  if (!out || !model || !sim || !task || !state) return fail(AS_ERR_INVALID, "as_create: null argument");
-  *out = nullptr;
-  if (num_envs <= 0) return fail(AS_ERR_INVALID, "as_create: num_envs must be > 0");
-  if (num_envs > AS_MAX_ENVS)
-    return fail(AS_ERR_INVALID, "as_create: num_envs > AS_MAX_ENVS (" + std::to_string(AS_MAX_ENVS) +
-                                    "): the kernels' state offsets are 32-bit; shard the envs over more handles");
-  if (model->num_links < 1 || model->num_links > as::kMaxLinks)
-    return fail(AS_ERR_INVALID, "as_create: num_links out of range (1.." + std::to_string(as::kMaxLinks) + ")");
-  if (model->num_hinges != model->num_links - 1 || model->num_hinges > AS_ACT_DIM)
-    return fail(AS_ERR_INVALID, "as_create: num_hinges must be num_links-1 <= 21");
-  if (model->num_geoms < 0 || model->num_geoms > AS_MAX_GEOMS) return fail(AS_ERR_INVALID, "as_create: num_geoms");
-  if (task->num_steps < 1 || task->num_steps > AS_NUM_STONES) return fail(AS_ERR_INVALID, "as_create: num_steps");
-  if (sim->substeps < 1 || sim->pgs_iters < 0) return fail(AS_ERR_INVALID, "as_create: substeps/pgs_iters");
-  const void* ptrs[] = {state->root_pos, state->root_quat, state->root_lin, state->root_ang, state->q,
-                        state->qd, state->stones, state->pot, state->old_pot, state->foot_contact,
-                        state->body_pos, state->idx, state->prev, state->next, state->count, state->swing,
-                        state->ep_len, state->episode, state->contact_mask, state->curriculum};
-  for (const void* p : ptrs)
-    if (!p) return fail(AS_ERR_INVALID, "as_create: null state field");
-  // every model field the kernels index with: a malformed model is rejected here instead of becoming
-  // an out-of-bounds LDS / register access (geoms: 32 LDS slots, foot id packed in 4 bits into the
-  // per-foot sensor masks; self pairs: 8-bit geom indices, 6 words per lane)
-  if (model->num_priority_geoms < 0 || model->num_priority_geoms > model->num_geoms)
-    return fail(AS_ERR_INVALID, "as_create: num_priority_geoms outside [0, num_geoms]");
-  const int max_foot = state->contact_mask_hind ? 3 : 1;
-  for (int g = 0; g < model->num_geoms; ++g) {
-    if (model->geom_link[g] < 0 || model->geom_link[g] >= model->num_links)
-      return fail(AS_ERR_INVALID, "as_create: geom_link[" + std::to_string(g) + "] outside [0, num_links)");
-    if (model->geom_type[g] != 0 && model->geom_type[g] != 1)
-      return fail(AS_ERR_INVALID, "as_create: geom_type[" + std::to_string(g) + "] not 0 (sphere) / 1 (capsule)");
-    if (model->geom_foot[g] < -1 || model->geom_foot[g] > max_foot)
-      return fail(AS_ERR_INVALID, "as_create: geom_foot[" + std::to_string(g) + "] outside [-1, " +
-                                      std::to_string(max_foot) + "] (2, 3 need contact_mask_hind)");
-  }
-  if (model->num_self_pairs < 0 || model->num_self_pairs > AS_MAX_SELF_PAIRS)
-    return fail(AS_ERR_INVALID, "as_create: num_self_pairs outside [0, AS_MAX_SELF_PAIRS]");
-  for (int i = 0; i < model->num_self_pairs; ++i) {
-    const int w = model->self_pair[i], g1 = w & 0xff, g2 = w >> 8;
-    if (w < 0 || g1 >= g2 || g2 >= model->num_geoms)
-      return fail(AS_ERR_INVALID, "as_create: self_pair[" + std::to_string(i) + "] is not g1 | g2 << 8 with g1 < g2 < num_geoms");
-  }
-
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(AS_ERR_NO_DEVICE, "as_create: no HIP device");
-  if (device < 0 || device >= ndev) return fail(AS_ERR_INVALID, "as_create: bad device index");
-  HIP_TRY(hipSetDevice(device));
-  hipDeviceProp_t prop;
-  HIP_TRY(hipGetDeviceProperties(&prop, device));
-  if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-    return fail(AS_ERR_NO_DEVICE, std::string("as_create: device is ") + prop.gcnArchName + ", built for gfx950");
-
-  // tree plan
-  as::Consts h{};
-  h.model = *model;
-  h.sim = *sim;
-  h.task = *task;
-  h.nv = 6 + model->num_hinges;
-  h.act.mode = AS_ACT_TORQUE;
-  h.st_has_hind = state->contact_mask_hind != nullptr;
-  const int nl = model->num_links;
-  for (int i = 0; i < nl; ++i) {
-    int pa = model->parent[i];
-    if (i == 0 ? pa != -1 : (pa < 0 || pa >= i)) return fail(AS_ERR_INVALID, "as_create: parent not topological");
-    h.lpath[i] = (i == 0 ? 0u : h.lpath[pa]) | (1u << i);
-    if (i > 0 && pa == 0) h.root_kids |= 1u << i;
-  }
-  for (int i = 0; i < nl; ++i)
-    for (int l = 0; l < nl; ++l)
-      if ((h.lpath[l] >> i) & 1u) h.lsub[i] |= 1u << l;
-  for (int j = 0; j < h.nv; ++j) h.dsub[j] = j < 6 ? h.lsub[0] : h.lsub[j - 5];
-  for (int i = 0; i < nl; ++i) {
-    h.max_path = std::max(h.max_path, __builtin_popcount(h.lpath[i]) - 1);
-    if (i > 0) h.max_sub = std::max(h.max_sub, __builtin_popcount(h.lsub[i]) - 1);
-  }
-  while ((1 << h.fk_rounds) < h.max_path) ++h.fk_rounds;
-  if (h.fk_rounds > 4) return fail(AS_ERR_INVALID, "as_create: tree deeper than 16 links");
-  for (int i = 0; i < nl; ++i) {
-    int a = i > 0 ? model->parent[i] : 0;
-    for (int r = 0; r < 4; ++r) {  // a = the 2^r-th ancestor (0 past the root)
-      h.jump[i] |= (uint32_t)a << (8 * r);
-      for (int k = 0; k < (1 << r); ++k) a = a > 0 ? model->parent[a] : 0;
-    }
-  }
-  for (int k = 0; k < model->num_hinges; ++k) {
-    int li = model->cfg_dof_link[k];
-    if (li < 1 || li >= model->num_links) return fail(AS_ERR_INVALID, "as_create: cfg_dof_link");
-  }
-  for (int l = 0; l < model->num_links; ++l) {
-    uint32_t mask = 0x3Fu;
-    for (int i = l; i > 0; i = model->parent[i]) mask |= 1u << (6 + i - 1);
-    h.ancmask[l] = mask;
-  }
-  for (int j = 0; j < h.nv; ++j)
-    for (int k = 0; k < h.nv; ++k) {
-      const int lk = k < 6 ? 0 : k - 5;
-      if ((h.ancmask[lk] >> j) & 1u) h.ddesc[j] |= 1u << k;
-    }
-  if (!as::step_supported_nv(h.nv))
-    return fail(AS_ERR_INVALID, "as_create: no k_step instantiation for " + std::to_string(h.nv) + " dofs");
-  as::fill_lane_table(h);
-  // collide pass B tests a stone pair on a group of up to 2^4 lanes (results are the same at any level);
-  // ALLSTEPS_PAIR_GROUP=1..4 caps the level, 1 = one lane per pair throughout (tests, A/B timing)
-  h.pair_group_cap = 4;
-  if (const char* pg = std::getenv("ALLSTEPS_PAIR_GROUP")) {
-    if (std::strlen(pg) != 1 || pg[0] < '1' || pg[0] > '4')
-      return fail(AS_ERR_INVALID, std::string("as_create: ALLSTEPS_PAIR_GROUP=") + pg + ", expected 1, 2, 3 or 4");
-    h.pair_group_cap = pg[0] - '0';
-  }
-
-  as_env* env = new as_env();
-  env->n = num_envs;
-  env->device = device;
-  env->seed = seed;
-  env->env_offset = env_id_offset;
-  env->st = *state;
-  env->num_steps = task->num_steps;
-  env->nv = h.nv;
-  env->host = h;
-  env->sweep_skip = as_sweep_plan(model, nullptr) == 1;
+// as_create's last step: the handle's device memory and the uploads.  On an error the caller destroys env.
+static int allocate_and_upload(as_env* env, const hipDeviceProp_t& prop) {
+  const int num_envs = env->n;
   if (hipMalloc(&env->consts_dev, sizeof(as::Consts)) != hipSuccess ||
       hipMalloc(&env->counters_dev, 2 * as::kCntBank * sizeof(int32_t)) != hipSuccess ||
-      hipMalloc(&env->side_dev, (size_t)as::kSideWords * num_envs * sizeof(uint32_t)) != hipSuccess) {
-    (void)hipFree(env->consts_dev);
-    (void)hipFree(env->counters_dev);
-    delete env;
+      hipMalloc(&env->side_dev, (size_t)as::kSideWords * num_envs * sizeof(uint32_t)) != hipSuccess)
     return fail(AS_ERR_HIP, "as_create: hipMalloc failed");
-  }
-  HIP_TRY(hipMemcpy(env->consts_dev, &h, sizeof(as::Consts), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(env->consts_dev, &env->host, sizeof(as::Consts), hipMemcpyHostToDevice));
   HIP_TRY(hipMemset(env->counters_dev, 0, 2 * as::kCntBank * sizeof(int32_t)));
   HIP_TRY(hipMemset(env->side_dev, 0, (size_t)as::kSideWords * num_envs * sizeof(uint32_t)));
   // cost-balanced placement (placement only: results are the same under any map); ALLSTEPS_WAVE_MAP=0
@@ -248,11 +127,81 @@ int as_create(int32_t num_envs, const as_model_t* model, const as_sim_t* sim, co
     for (int w = 0; w < num_envs / as::kMapEnvs; ++w)
       for (int t = 0; t < as::kMapEnvs; ++t)
         map[(size_t)2 * as::wave_map_block(w, t >> 1, num_envs, env->map_streamed) + (t & 1)] = w * as::kMapEnvs + t;
-    if (hipMalloc(&env->wave_map_dev, map.size() * sizeof(int32_t)) != hipSuccess) {
-      (void)as_destroy(env);
+    if (hipMalloc(&env->wave_map_dev, map.size() * sizeof(int32_t)) != hipSuccess)
       return fail(AS_ERR_HIP, "as_create: hipMalloc failed");
-    }
     HIP_TRY(hipMemcpy(env->wave_map_dev, map.data(), map.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  }
+  return AS_OK;
+}
+
+int as_create(int32_t num_envs, const as_model_t* model, const as_sim_t* sim, const as_task_t* task,
+              const as_state_t* state, uint64_t seed, int32_t device, int64_t env_id_offset, as_env_t** out) {
+  // 1. arguments
+  if (!out || !model || !sim || !task || !state) return fail(AS_ERR_INVALID, "as_create: null argument");
+  *out = nullptr;
+  if (num_envs <= 0) return fail(AS_ERR_INVALID, "as_create: num_envs must be > 0");
+  if (num_envs > AS_MAX_ENVS)
+    return fail(AS_ERR_INVALID, "as_create: num_envs > AS_MAX_ENVS (" + std::to_string(AS_MAX_ENVS) +
+                                    "): the kernels' state offsets are 32-bit; shard the envs over more handles");
+  if (task->num_steps < 1 || task->num_steps > AS_NUM_STONES) return fail(AS_ERR_INVALID, "as_create: num_steps");
+  if (sim->substeps < 1 || sim->pgs_iters < 0) return fail(AS_ERR_INVALID, "as_create: substeps/pgs_iters");
+  const void* ptrs[] = {state->root_pos, state->root_quat, state->root_lin, state->root_ang, state->q,
+                        state->qd, state->stones, state->pot, state->old_pot, state->foot_contact,
+                        state->body_pos, state->idx, state->prev, state->next, state->count, state->swing,
+                        state->ep_len, state->episode, state->contact_mask, state->curriculum};
+  for (const void* p : ptrs)
+    if (!p) return fail(AS_ERR_INVALID, "as_create: null state field");
+
+  // 2. model
+  std::string err;
+  if (!as::check_model(*model, state->contact_mask_hind != nullptr, err)) return fail(AS_ERR_INVALID, "as_create: " + err);
+
+  // 3. device
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(AS_ERR_NO_DEVICE, "as_create: no HIP device");
+  if (device < 0 || device >= ndev) return fail(AS_ERR_INVALID, "as_create: bad device index");
+  HIP_TRY(hipSetDevice(device));
+  hipDeviceProp_t prop;
+  HIP_TRY(hipGetDeviceProperties(&prop, device));
+  if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+    return fail(AS_ERR_NO_DEVICE, std::string("as_create: device is ") + prop.gcnArchName + ", built for gfx950");
+
+  // 4. plan: the constants block with the tree plan and the lane table
+  as::Consts h{};
+  h.model = *model;
+  h.sim = *sim;
+  h.task = *task;
+  h.nv = 6 + model->num_hinges;
+  h.act.mode = AS_ACT_TORQUE;
+  h.st_has_hind = state->contact_mask_hind != nullptr;
+  if (!as::plan_tree(h, err)) return fail(AS_ERR_INVALID, "as_create: " + err);
+  if (!as::step_supported_nv(h.nv))
+    return fail(AS_ERR_INVALID, "as_create: no k_step instantiation for " + std::to_string(h.nv) + " dofs");
+  as::fill_lane_table(h);
+  // collide pass B tests a stone pair on a group of up to 2^4 lanes (results are the same at any level);
+  // ALLSTEPS_PAIR_GROUP=1..4 caps the level, 1 = one lane per pair throughout (tests, A/B timing)
+  h.pair_group_cap = 4;
+  if (const char* pg = std::getenv("ALLSTEPS_PAIR_GROUP")) {
+    if (std::strlen(pg) != 1 || pg[0] < '1' || pg[0] > '4')
+      return fail(AS_ERR_INVALID, std::string("as_create: ALLSTEPS_PAIR_GROUP=") + pg + ", expected 1, 2, 3 or 4");
+    h.pair_group_cap = pg[0] - '0';
+  }
+
+  // 5. allocate and upload; past this point every failure destroys the handle
+  as_env* env = new as_env();
+  env->n = num_envs;
+  env->device = device;
+  env->seed = seed;
+  env->env_offset = env_id_offset;
+  env->st = *state;
+  env->num_steps = task->num_steps;
+  env->nv = h.nv;
+  env->host = h;
+  env->sweep_skip = as_sweep_plan(model, nullptr) == 1;
+  const int rc = allocate_and_upload(env, prop);
+  if (rc != AS_OK) {
+    (void)as_destroy(env);
+    return rc;
   }
   *out = env;
   return AS_OK;
@@ -413,6 +362,16 @@ int as_physics_step(as_env_t* env, const float* actions, void* stream) {
   return run(env, as::kModePhysics, actions, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
+// The setters' common end: env->host changed, so rebuild the lane table and replace the device block.
+static int upload_consts(as_env_t* env) {
+  as::fill_lane_table(env->host);
+  // setup call, not stream-ordered: every launch still queued on any stream (torch's pool streams are
+  // non-blocking, so a plain hipMemcpy would not wait for them) finishes before the block changes
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(env->consts_dev, &env->host, sizeof(as::Consts), hipMemcpyHostToDevice));
+  return AS_OK;
+}
+
 int as_set_actuator(as_env_t* env, const as_actuator_t* act) {
   if (!env || !act) return fail(AS_ERR_INVALID, "as_set_actuator: null argument");
   if (act->mode != AS_ACT_TORQUE && act->mode != AS_ACT_DC_MOTOR) return fail(AS_ERR_INVALID, "as_set_actuator: mode");
@@ -420,13 +379,7 @@ int as_set_actuator(as_env_t* env, const as_actuator_t* act) {
     return fail(AS_ERR_INVALID, "as_set_actuator: the DC motor needs velocity_limit > 0 and effort_limit >= 0");
   HIP_TRY(hipSetDevice(env->device));
   env->host.act = *act;
-  as::fill_lane_table(env->host);
-  // ordered on the null stream with respect to every earlier launch (hipMemcpy synchronises)
-  // setup call, not stream-ordered: every launch still queued on any stream (torch's pool streams are
-  // non-blocking, so a plain hipMemcpy would not wait for them) finishes before the block changes
-  HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(env->consts_dev, &env->host, sizeof(as::Consts), hipMemcpyHostToDevice));
-  return AS_OK;
+  return upload_consts(env);
 }
 
 int as_set_quad_task(as_env_t* env, const as_quad_task_t* q) {
@@ -445,11 +398,8 @@ int as_set_quad_task(as_env_t* env, const as_quad_task_t* q) {
   }
   HIP_TRY(hipSetDevice(env->device));
   env->host.quad = *q;
-  as::fill_lane_table(env->host);
-  // setup call, not stream-ordered: every launch still queued on any stream (torch's pool streams are
-  // non-blocking, so a plain hipMemcpy would not wait for them) finishes before the block changes
-  HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(env->consts_dev, &env->host, sizeof(as::Consts), hipMemcpyHostToDevice));
+  const int rc = upload_consts(env);
+  if (rc != AS_OK) return rc;
   env->quad_ready = 1;
   return AS_OK;
 }

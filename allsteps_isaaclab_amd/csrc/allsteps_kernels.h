@@ -5,51 +5,13 @@
 #include <stdint.h>
 
 #include "../../include/allsteps.h"
+#include "allsteps_consts.h"
 #include "allsteps_lane_table.h"
 #include "allsteps_pair_group.h"
 
 namespace as {
 
-constexpr int kMaxLinks = 24;  // LDS sizing of the step kernel (walker: 22 links)
-constexpr int kMaxDofs = 6 + kMaxLinks - 1;
-
 enum { kModeStep = 0, kModeReset = 1, kModePhysics = 2, kModeTask = 3 };
-
-// Everything the kernels read that does not change per step: model tables + the tree plan
-// derived from them on the host.  The plan is bitmasks over links / dofs: every tree pass of the
-// step kernel is a walk over one lane's own ancestor path or subtree (no level barriers), and
-// each lane keeps its own masks in registers for the whole launch.
-struct Consts {
-  as_model_t model;
-  as_sim_t sim;
-  as_task_t task;
-  as_actuator_t act;               // as_set_actuator (mode AS_ACT_TORQUE after as_create)
-  as_quad_task_t quad;             // as_set_quad_task (BASELINE C5)
-  int32_t nv;
-  int32_t st_has_hind;             // the state carries contact_mask_hind (sensors 2, 3)
-  int32_t max_path;                // longest root->link path, root excluded (links)
-  int32_t max_sub;                 // largest subtree of a non-root link, itself excluded
-  uint32_t root_kids;              // links whose parent is the root
-  uint32_t lpath[kMaxLinks];       // links on the path root..link, both included
-  uint32_t lsub[kMaxLinks];        // links in the subtree of link, itself included
-  uint32_t ancmask[kMaxLinks];     // dofs on the path root..link (root dofs 0-5 always set)
-  uint32_t dsub[kMaxDofs];         // links moved by dof j (subtree of its link; root dofs: all)
-  uint32_t ddesc[kMaxDofs];        // dofs k whose link path contains dof j (bit k)
-  // FK by pointer jumping (k_step fk): jump[i] byte r = the 2^r-th ancestor of link i, the root (0)
-  // once the path is exhausted; fk_rounds = ceil(log2(max_path)) rounds cover every path
-  uint32_t jump[kMaxLinks];
-  int32_t fk_rounds;
-  // collide pass B: the largest lane-group level per stone pair (allsteps_pair_group.h): 4, or what
-  // ALLSTEPS_PAIR_GROUP set at as_create (1: one lane per pair, always)
-  int32_t pair_group_cap;
-  // everything lane-indexed that k_step reads once per launch, one row per lane (allsteps_lane_table.h);
-  // rebuilt by fill_lane_table whenever the model, task or actuator fields above change
-  LaneRow lane[kLaneRows];
-};
-static_assert(kLaneRows == 32 && kMaxLinks <= kLaneRows && kMaxDofs <= kLaneRows, "one table row per k_step lane");
-inline void fill_lane_table(Consts& c) {
-  build_lane_table(c.lane, c.model, c.task, c.act, c.nv, c.lpath, c.lsub, c.ancmask, c.dsub, c.jump);
-}
 
 struct StepArgs {
   const Consts* consts;
@@ -168,15 +130,6 @@ struct BodyArgs {
   float* out;                  // [AS_BODY_STATE_ROWS][nb][n]
   as_body_table_t bodies;
 };
-
-// The H^-1 sweep's skipped column quads (allsteps_kernels.hip sweep_inverse; bit r (NB - 1) + jb: round
-// r, quad jb of the rotated row), compiled for the Allsteps walker (27 dofs) and the C5 quadruped (18):
-// the quads in which the pivot rows are structurally zero for those trees.  as_create runs the
-// structural sweep for the model it is given (sweep_skip_mask) and launches the skipping kernel only if
-// every compiled bit is also set for that model.
-constexpr uint64_t kSweepSkip27 = 207817167ull;  // 14 of the walker's 42 quad updates
-constexpr uint64_t kSweepSkip18 = 3219ull;       // 6 of the quadruped's 20
-uint64_t sweep_skip_mask(const as_model_t& m);  // the model's exactly-zero quads (host)
 
 bool step_supported_nv(int nv);
 hipError_t launch_body_state(const BodyArgs& a, hipStream_t stream);

@@ -5,7 +5,7 @@ stepping stones (the reference renders through Isaac Sim's RTX viewport, absent 
 The frame is a side view (world x right, z up) of env ``env_id`` with a top view (x right, y up) inset:
 stones as boxes, the robot's sphere / capsule geoms as discs / stadiums.  Link poses come from a host
 forward kinematics of the device state (root pose + joint angles) over the model tables -- the same
-local-transform composition as the k_step FK (``csrc/allsteps_kernels.hip`` fk), evaluated in float64 for
+local-transform composition as the k_step FK (``csrc/step_dynamics.h`` fk), evaluated in float64 for
 one env per frame.  Rendering is a viewer, not part of the stepped path: it reads the state and draws.
 """
 

@@ -28,7 +28,7 @@
 #define AS_HD static inline
 #endif
 
-/* The H^-1 sweep's layout (csrc/allsteps_kernels.hip sweep_inverse, oracle/physics.c sweep_inverse):
+/* The H^-1 sweep's layout (csrc/step_dynamics.h sweep_inverse, oracle/physics.c sweep_inverse):
  * the nv dofs are padded to a multiple of 4 with identity rows / columns inserted at padded index
  * AS_SWEEP_PAD(nv) (dof k < pad -> k, else k + the pad count), and the 4 x 4 pivot blocks are swept
  * LAST block first -- the limbs (the high dof indices of a topological order) before the root, so the

@@ -87,7 +87,7 @@ static int is_ancestor(const or_model_t* m, int a, int l) {
 }
 
 /* Subtree sums as the HIP kernel's matrix product forms them (dynamics() in
- * csrc/allsteps_kernels.hip: the two-block f32 MFMA over OR_SUBTREE_STEPS K steps, one per link
+ * csrc/step_dynamics.h: the two-block f32 MFMA over OR_SUBTREE_STEPS K steps, one per link
  * slot): for every link i, one fmaf chain from +0 over the link slots l ascending,
  * acc = fmaf(x_l, [l in subtree(i)], acc), with x_l = 0 past the model's links; subtree(i) includes
  * i, and the root's is the whole tree. */
@@ -301,7 +301,7 @@ static void rnea_bias(const or_model_t* m, const kin_t* K, const float* u, float
 
 /* Inverse of the SPD joint-space inertia by the block sweep operator on SWEEP_B x SWEEP_B pivot
  * blocks (no pivoting needed for SPD), in the arithmetic of the HIP kernel (sweep_inverse /
- * block_inverse in csrc/allsteps_kernels.hip).  The matrix is padded to a multiple of SWEEP_B with
+ * block_inverse in csrc/step_dynamics.h).  The matrix is padded to a multiple of SWEEP_B with
  * identity rows/columns at AS_SWEEP_PAD(n), and the blocks are swept last block first (the limbs
  * before the root).  Round on P = {p..p+B-1}: D = (a_PP)^-1 by 2x2-block Schur complement;
  * row'_j = alpha a_ij - sum_c beta_c a_Pc,j for j not in P, row'_P = beta, where

@@ -1,7 +1,7 @@
 /*
  * quad.c -- CPU restatement of the BASELINE C5 quadruped task (TEST INFRASTRUCTURE; see oracle.h).
  *
- * The serial form of the HIP kernel k_quad (allsteps_isaaclab_amd/csrc/allsteps_kernels.hip) and of
+ * The serial form of the HIP kernel k_quad (allsteps_isaaclab_amd/csrc/task_kernels.h) and of
  * include/allsteps.h as_quad_task_t.  The reference has no quadruped stepping-stone task (its ANYmal-C
  * task, isaaclab_tasks/direct/anymal_c/anymal_c_env.py, is flat-ground velocity tracking): the task is
  * authored here from the Allsteps task's pieces (target stones, potentials, allsteps_env.py:347-457)

@@ -1,11 +1,14 @@
 #!/bin/bash
-# build an A/B candidate step library into abtest/ (scratch, git-ignored): bash scripts/ab_build.sh NAME KERNELS.hip [extra hipcc flags]
-# (KERNELS.hip: a copy of csrc/allsteps_kernels.hip; its includes are rewritten to this tree's paths)
+# build an A/B candidate step library into abtest/ (scratch, git-ignored): bash scripts/ab_build.sh NAME CSRC_COPY_DIR [extra hipcc flags]
+# (CSRC_COPY_DIR: a whole copy of allsteps_isaaclab_amd/csrc, e.g. `cp -r allsteps_isaaclab_amd/csrc abtest/csrc_NAME`,
+#  with the phase header under test edited: its allsteps_kernels.hip is compiled, every "x.h" it includes is the
+#  copy's own, and -iquote resolves its ../../include paths from this tree's csrc; allsteps_abi.hip is this tree's)
 set -e
 cd "$(dirname "$0")/.."
 N=$1; SRC=$2; shift 2
-T=abtest/.src_$N.hip
-sed 's#"../../include/allsteps.h"#"../include/allsteps.h"#; s#"allsteps_device.h"#"../allsteps_isaaclab_amd/csrc/allsteps_device.h"#; s#"allsteps_kernels.h"#"../allsteps_isaaclab_amd/csrc/allsteps_kernels.h"#' $SRC > $T
+[ -f "$SRC/allsteps_kernels.hip" ] || { echo "usage: ab_build.sh NAME CSRC_COPY_DIR [flags]: no $SRC/allsteps_kernels.hip" >&2; exit 2; }
+mkdir -p abtest
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-slp-vectorize -I include \
-  -DAS_BUILD_ID=\"abtest-$N\" -fPIC -shared -Wno-unused-result "$@" -o abtest/$N.so $T allsteps_isaaclab_amd/csrc/allsteps_abi.hip
+  -iquote allsteps_isaaclab_amd/csrc -DAS_BUILD_ID=\"abtest-$N\" -fPIC -shared -Wno-unused-result "$@" \
+  -o abtest/$N.so "$SRC/allsteps_kernels.hip" allsteps_isaaclab_amd/csrc/allsteps_abi.hip
 echo built abtest/$N.so

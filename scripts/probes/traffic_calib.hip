@@ -28,7 +28,7 @@
     }                                                                                \
   } while (0)
 
-// the same mapping as csrc/allsteps_kernels.hip xcd_block
+// the same mapping as csrc/step_task.h xcd_block
 __device__ __forceinline__ int xcd_block(int b, int nb) {
   const int q = nb >> 3, r = nb & 7, x = b & 7, slot = b >> 3;
   return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + slot;

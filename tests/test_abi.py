@@ -265,7 +265,7 @@ def test_loader_refuses_a_library_built_from_other_sources(monkeypatch):
 
 
 def _structural_skip_mask(m: dict) -> int:
-    """Python restatement of the kernel's structural sweep (csrc/allsteps_kernels.hip sweep_skip_mask):
+    """Python restatement of the kernel's structural sweep (csrc/allsteps_consts.h sweep_skip_mask):
     padded layout AS_SWEEP_PAD, last block first, a quad skippable when the pivot rows are zero there."""
     import numpy as np
 
@@ -326,4 +326,9 @@ def test_sweep_plan_skips_only_structural_zeros():
     bad = dict(walker)
     bad["parent"] = [-1, 3] + list(walker["parent"][2:])
     with pytest.raises(_native.NativeError, match="topological"):
+        _native.sweep_plan(bad)
+    # the model checks are as_create's: a hinge count that is not num_links - 1 is refused, not swept
+    bad = dict(walker)
+    bad["num_hinges"] = walker["num_hinges"] - 1
+    with pytest.raises(_native.NativeError, match="num_hinges"):
         _native.sweep_plan(bad)
