@@ -18,16 +18,21 @@ CSRC = os.path.join(PKG, "csrc")
 INCLUDE = os.path.join(os.path.dirname(PKG), "include")
 
 MAXL, MAXG, MAXSP = 32, 32, 256
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 EXPORTED_SYMBOLS = [
     "as_create", "as_destroy", "as_reset_all", "as_step", "as_physics_step", "as_generate_stones",
     "as_step_counters", "as_get_curriculum_host", "as_abi_version", "as_last_error", "as_task_step",
     "as_set_seed", "as_profile", "as_profile_read", "as_debug_stamps", "as_reset_mask", "as_set_graph_safe",
     "as_profile_sampled", "as_hbm_copy", "as_set_actuator", "as_set_quad_task", "as_quad_step", "as_quad_reset_all",
-    "as_build_id", "as_step_counters_host", "as_body_state", "as_sweep_plan",
+    "as_build_id", "as_step_counters_host", "as_body_state", "as_sweep_plan", "as_set_contact_report",
+    "as_contact_forces",
 ]
 MAXB = 32  # AS_MAX_BODIES
+MAXC = 10  # AS_MAX_CONTACTS
+REPORT_WORDS = 8  # AS_REPORT_WORDS: lambda_n n (3) | contact point (3) | separation | packed ids
+REPORT_FEET = 4  # AS_REPORT_FEET
+NUM_STONES = 20  # AS_NUM_STONES
 BODY_STATE_ROWS = 16  # AS_BODY_STATE_ROWS: pos 3 | quat 4 | frame lin vel 3 | ang vel 3 | COM lin vel 3
 
 
@@ -39,6 +44,16 @@ class AsBodyTable(C.Structure):
     """as_body_table_t (include/allsteps.h): the model's bodies for as_body_state."""
     _fields_ = [("num_bodies", C.c_int32), ("link", C.c_int32 * MAXB), ("offset_pos", (C.c_float * 3) * MAXB),
                 ("offset_quat", (C.c_float * 4) * MAXB), ("com", (C.c_float * 3) * MAXB)]
+
+
+class AsContactReport(C.Structure):
+    """as_contact_report_t (include/allsteps.h): caller-owned device buffers of the opt-in contact report."""
+    _fields_ = [("depth", C.c_int32), ("count", C.c_void_p), ("records", C.c_void_p), ("qd_prev", C.c_void_p)]
+
+
+def unpack_report_ids(w):
+    """(link, link2, stone, foot) of a record's ids word (int array or tensor); -1 = none."""
+    return w & 0xFF, (w >> 8 & 0xFF) - 1, (w >> 16 & 0xFF) - 1, (w >> 24 & 0xFF) - 1
 
 
 def make_body_table(m: dict) -> AsBodyTable:
@@ -201,6 +216,8 @@ def load() -> C.CDLL:
     L.as_quad_reset_all.argtypes = [V, V, V]
     L.as_body_state.argtypes = [V, V, V, V]
     L.as_sweep_plan.argtypes = [V, C.POINTER(C.c_uint64)]
+    L.as_set_contact_report.argtypes = [V, V]
+    L.as_contact_forces.argtypes = [V, V, V, V, V]
     L.as_last_error.restype = C.c_char_p
     L.as_build_id.restype = C.c_char_p
     for name in EXPORTED_SYMBOLS:
@@ -406,6 +423,26 @@ class NativeEnv:
     def body_state(self, table: "AsBodyTable", out, stream=None):
         """as_body_state: out [BODY_STATE_ROWS][num_bodies][n] fp32 on the device (ring-2 body views)."""
         check(self.L.as_body_state(self.h, C.byref(table), out.data_ptr(), stream), "as_body_state")
+
+    def set_contact_report(self, depth: int = 0, count=None, records=None, qd_prev=None):
+        """as_set_contact_report over caller-owned device tensors: count int32 [depth][n], records int32
+        [depth][REPORT_WORDS][MAXC][n], qd_prev fp32 [21][n] (kept alive here); no tensors: report off."""
+        if count is None and records is None and qd_prev is None:
+            self._report = None
+            check(self.L.as_set_contact_report(self.h, None), "as_set_contact_report")
+            return
+        R = AsContactReport()
+        R.depth = int(depth)
+        R.count, R.records, R.qd_prev = (None if t is None else t.data_ptr() for t in (count, records, qd_prev))
+        check(self.L.as_set_contact_report(self.h, C.byref(R)), "as_set_contact_report")
+        self._report = (R, count, records, qd_prev)
+
+    def contact_forces(self, table: "AsBodyTable", force_matrix_out, net_out, stream=None):
+        """as_contact_forces: force_matrix_out fp32 [depth][REPORT_FEET][NUM_STONES][3][n], net_out fp32
+        [depth][num_bodies][3][n] (impulses, N s) from the report as it stands."""
+        check(self.L.as_contact_forces(self.h, C.byref(table) if table is not None else None,
+                                       None if force_matrix_out is None else force_matrix_out.data_ptr(),
+                                       None if net_out is None else net_out.data_ptr(), stream), "as_contact_forces")
 
     def set_actuator(self, mode: int, action_scale: float = 0.0, default_q=(), stiffness: float = 0.0,
                      damping: float = 0.0, saturation_effort: float = 0.0, effort_limit: float = 0.0,

@@ -66,6 +66,8 @@ struct as_env {
   // optional per-launch timing (as_profile): event triples around k_step / k_obs
   std::vector<hipEvent_t> ev;
   unsigned long long* stamps = nullptr;  // diagnostic (as_debug_stamps)
+  as_contact_report_t report{};          // as_set_contact_report (count == nullptr: off)
+  as::ReportDesc* report_dev = nullptr;  // its device copy, the block the launches point at
   int32_t prof_cap = 0, prof_n = 0, prof_stride = 1, prof_calls = 0;
 };
 
@@ -111,7 +113,8 @@ static int allocate_and_upload(as_env* env, const hipDeviceProp_t& prop) {
   const int num_envs = env->n;
   if (hipMalloc(&env->consts_dev, sizeof(as::Consts)) != hipSuccess ||
       hipMalloc(&env->counters_dev, 2 * as::kCntBank * sizeof(int32_t)) != hipSuccess ||
-      hipMalloc(&env->side_dev, (size_t)as::kSideWords * num_envs * sizeof(uint32_t)) != hipSuccess)
+      hipMalloc(&env->side_dev, (size_t)as::kSideWords * num_envs * sizeof(uint32_t)) != hipSuccess ||
+      hipMalloc(&env->report_dev, sizeof(as::ReportDesc)) != hipSuccess)
     return fail(AS_ERR_HIP, "as_create: hipMalloc failed");
   HIP_TRY(hipMemcpy(env->consts_dev, &env->host, sizeof(as::Consts), hipMemcpyHostToDevice));
   HIP_TRY(hipMemset(env->counters_dev, 0, 2 * as::kCntBank * sizeof(int32_t)));
@@ -215,6 +218,7 @@ int as_destroy(as_env_t* env) {
   (void)hipFree(env->counters_dev);
   (void)hipFree(env->side_dev);
   (void)hipFree(env->wave_map_dev);
+  (void)hipFree(env->report_dev);
   delete env;
   return AS_OK;
 }
@@ -249,6 +253,7 @@ static int run(as_env_t* env, int mode, const float* actions, float* obs, float*
   a.obs = mode == as::kModePhysics ? nullptr : obs;
   a.side = env->side_dev;
   a.wave_map = env->wave_map_dev;
+  a.rep = env->report.count ? env->report_dev : nullptr;
   const bool prof = env->prof_n < env->prof_cap && (env->prof_calls++ % env->prof_stride) == 0;
   if (prof) HIP_TRY(hipEventRecord(env->ev[3 * env->prof_n], s));
   HIP_TRY(as::launch_step(a, env->nv, env->sweep_skip, s));
@@ -427,6 +432,7 @@ static int quad(as_env_t* env, int reset_all, const float* actions, float* obs, 
   a.side = env->side_dev;
   a.wave_map = env->wave_map_dev;
   a.map_streamed = env->map_streamed;
+  a.rep = env->report.count ? env->report_dev : nullptr;
   HIP_TRY(as::launch_quad(a, s));
   return AS_OK;
 }
@@ -473,6 +479,51 @@ int as_body_state(as_env_t* env, const as_body_table_t* bodies_host, float* out,
   a.out = out;
   a.bodies = b;
   HIP_TRY(as::launch_body_state(a, reinterpret_cast<hipStream_t>(stream)));
+  return AS_OK;
+}
+
+int as_set_contact_report(as_env_t* env, const as_contact_report_t* report) {
+  if (!env) return fail(AS_ERR_INVALID, "as_set_contact_report: null handle");
+  if (!report) {
+    env->report = as_contact_report_t{};
+    return AS_OK;
+  }
+  if (!report->count || !report->records || !report->qd_prev)
+    return fail(AS_ERR_INVALID, "as_set_contact_report: null buffer (count / records / qd_prev)");
+  if (report->depth < 1 || report->depth > env->host.sim.substeps)
+    return fail(AS_ERR_INVALID, "as_set_contact_report: depth " + std::to_string(report->depth) +
+                                    " outside [1, sim.substeps = " + std::to_string(env->host.sim.substeps) + "]");
+  // setup call, not stream-ordered (as upload_consts): queued launches finish before the block changes
+  const as::ReportDesc d{report->count, report->records, report->qd_prev, report->depth};
+  HIP_TRY(hipSetDevice(env->device));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(env->report_dev, &d, sizeof(d), hipMemcpyHostToDevice));
+  env->report = *report;
+  return AS_OK;
+}
+
+int as_contact_forces(as_env_t* env, const as_body_table_t* bodies_host, float* force_matrix_out, float* net_out,
+                      void* stream) {
+  if (!env || !bodies_host || !force_matrix_out || !net_out)
+    return fail(AS_ERR_INVALID, "as_contact_forces: null argument");
+  if (!env->report.count) return fail(AS_ERR_INVALID, "as_contact_forces: no contact report set (as_set_contact_report)");
+  const as_body_table_t& b = *bodies_host;
+  if (b.num_bodies < 1 || b.num_bodies > AS_MAX_BODIES)
+    return fail(AS_ERR_INVALID, "as_contact_forces: num_bodies out of range [1, AS_MAX_BODIES]");
+  as::ForcesArgs a{};
+  for (int i = 0; i < b.num_bodies; ++i) {
+    if (b.link[i] < 0 || b.link[i] >= env->host.model.num_links)
+      return fail(AS_ERR_INVALID, "as_contact_forces: body link out of range");
+    a.link[i] = b.link[i];
+  }
+  a.n = env->n;
+  a.depth = env->report.depth;
+  a.count = env->report.count;
+  a.records = env->report.records;
+  a.matrix = force_matrix_out;
+  a.net = net_out;
+  a.num_bodies = b.num_bodies;
+  HIP_TRY(as::launch_contact_forces(a, reinterpret_cast<hipStream_t>(stream)));
   return AS_OK;
 }
 

@@ -6,10 +6,21 @@
 
 #include "../../include/allsteps.h"
 #include "allsteps_consts.h"
+#include "allsteps_contact_report.h"
 #include "allsteps_lane_table.h"
 #include "allsteps_pair_group.h"
 
 namespace as {
+
+// The contact report's buffers (as_contact_report_t) as the kernels read them: a block in device memory that
+// as_set_contact_report fills, so that a launch carries one pointer and k_step reads the rest (uniform: scalar
+// loads) only where it stores.
+struct ReportDesc {
+  int32_t* count;
+  uint32_t* records;
+  float* qd_prev;
+  int32_t depth;
+};
 
 enum { kModeStep = 0, kModeReset = 1, kModePhysics = 2, kModeTask = 3 };
 
@@ -31,6 +42,7 @@ struct StepArgs {
   int64_t env_offset;
   unsigned long long* stamps;  // diagnostic phase timing (s_memtime deltas summed over waves) or null
   const int32_t* wave_map;     // [2 * blocks] env of each workgroup half (see kMapEnvs) or null: xcd_block
+  const ReportDesc* rep;       // the opt-in contact report (step_report.h), or null: off
 };
 
 // phase ids of the diagnostic stamps (as_debug_stamps)
@@ -95,6 +107,7 @@ struct QuadArgs {
   const uint32_t* side;        // k_step's side buffer (the row counts of the placement)
   int32_t* wave_map;           // null, or rebuilt here for the next k_step (kMapEnvs)
   int32_t map_streamed;        // wave_map_block
+  const ReportDesc* rep;       // the contact report, whose counts are cleared for the envs reset here, or null
 };
 
 struct ObsArgs {
@@ -131,7 +144,20 @@ struct BodyArgs {
   as_body_table_t bodies;
 };
 
+// k_contact_forces (as_contact_forces): dense sums over the contact report
+struct ForcesArgs {
+  int32_t n;
+  int32_t depth;
+  const int32_t* count;
+  const uint32_t* records;
+  float* matrix;               // [depth][AS_REPORT_FEET][AS_NUM_STONES][3][n]
+  float* net;                  // [depth][nb][3][n]
+  int32_t num_bodies;
+  int32_t link[AS_MAX_BODIES];
+};
+
 bool step_supported_nv(int nv);
+hipError_t launch_contact_forces(const ForcesArgs& a, hipStream_t stream);
 hipError_t launch_body_state(const BodyArgs& a, hipStream_t stream);
 hipError_t launch_step(const StepArgs& a, int nv, bool sweep_skip, hipStream_t stream);
 hipError_t launch_obs(const ObsArgs& a, hipStream_t stream);

@@ -22,8 +22,10 @@
 // This file is the one translation unit: k_step and the launchers.  Everything k_step calls is in the phase
 // headers below, included in definition order (the order also fixes the order of the compiled listing):
 //   step_scratch.h  LDS layout -> step_lanes.h  cross-lane primitives -> step_dynamics.h  FK, dynamics,
-//   H^-1 sweep -> step_collide.h  contacts -> step_solve.h  rows, PGS, substep -> step_task.h  task helpers;
-// after k_step: task_kernels.h (k_obs, k_stones, k_quad) and body_state_kernel.h (k_body_state).
+//   H^-1 sweep -> step_collide.h  contacts -> step_solve.h  rows, PGS, substep -> step_report.h  the opt-in
+//   contact report's stores -> step_task.h  task helpers;
+// after k_step: task_kernels.h (k_obs, k_stones, k_quad), body_state_kernel.h (k_body_state) and
+// contact_forces_kernel.h (k_contact_forces).
 #include <hip/hip_runtime.h>
 
 #include "../../include/allsteps.h"
@@ -35,6 +37,7 @@
 #include "step_dynamics.h"
 #include "step_collide.h"
 #include "step_solve.h"
+#include "step_report.h"
 #include "step_task.h"
 
 namespace as {
@@ -156,7 +159,19 @@ __global__ __launch_bounds__(kStepThreads) __attribute__((amdgpu_waves_per_eu(2,
   // ---- physics
   if (do_physics) {
     const int substeps = Kc->sim.substeps;  // (through the generic reference it was re-read every substep)
-    for (int sub = 0; sub < substeps; ++sub) substep<NV, SKIP>(K, sm, s, lane, tp, gc, lc, mask, ts);
+    // (counted down: `left` substeps follow this one, which is also its slot in the contact report)
+    for (int left = substeps - 1; left >= 0; --left) {
+      // the opt-in contact report (step_report.h): a wave-uniform test of a launch argument per substep
+      // (each test on an opaque copy of the pointer: no predicate of it is formed ahead of the loop and
+      // held, spilled, across the substeps)
+      const ReportDesc* rp = P.rep;
+      asm volatile("" : "+s"(rp));
+      if (rp && left == 0) report_store_qd(rp, n, Kc, s, lane, e, valid);
+      substep<NV, SKIP>(K, sm, s, lane, tp, gc, lc, mask, ts);
+      rp = P.rep;
+      asm volatile("" : "+s"(rp));
+      if (rp) report_store(rp, n, s, lane, e, valid, left);
+    }
   }
   // This lane's reset constants (joint `lane` in cfg order: its link and limits, the start pose plain and
   // mirrored), loaded ahead of the final FK so that their global loads (L2 round trips) run under it
@@ -441,6 +456,7 @@ __global__ __launch_bounds__(kStepThreads) __attribute__((amdgpu_waves_per_eu(2,
 
 #include "task_kernels.h"
 #include "body_state_kernel.h"
+#include "contact_forces_kernel.h"
 
 namespace as {
 
@@ -488,6 +504,12 @@ hipError_t launch_quad(const QuadArgs& a, hipStream_t stream) {
 hipError_t launch_body_state(const BodyArgs& a, hipStream_t stream) {
   const int blocks = (a.n + EPB - 1) / EPB;
   hipLaunchKernelGGL(k_body_state, dim3(blocks), dim3(kStepThreads), 0, stream, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_contact_forces(const ForcesArgs& a, hipStream_t stream) {
+  const int blocks = (a.n + kForcesThreads - 1) / kForcesThreads;
+  hipLaunchKernelGGL(k_contact_forces, dim3(blocks, a.depth), dim3(kForcesThreads), 0, stream, a);
   return hipGetLastError();
 }
 

@@ -353,6 +353,9 @@ __global__ __launch_bounds__(4 * kQuadEnvs) void k_quad(QuadArgs P) {
       st.contact_mask[n + e] = 0u;
       st.contact_mask_hind[e] = 0u;
       st.contact_mask_hind[n + e] = 0u;
+      // the contact report follows the masks: no contacts in any stored substep of a reset env
+      if (P.rep)
+        for (int k = 0; k < P.rep->depth; ++k) P.rep->count[report_count_index(k, e, n)] = 0;
     }
     st.idx[e] = idx;
     for (int f = 0; f < 4; ++f) {

@@ -65,6 +65,14 @@ class _RobotData:
     joint_vel = property(lambda self: self._s["qd"][: self._nd].T)
 
     @property
+    def joint_acc(self) -> torch.Tensor:
+        """(N, nd) joint accelerations: the last physics substep's finite difference (joint_vel - the velocity
+        at that substep's start) / sim.dt (articulation_data.py:78-83, 547-556), from the contact report's
+        qd_prev -- cfg.contact_forces only.  An env the step reset shows its reset velocity against the old one."""
+        rep = self._env._report_or_raise("robot.data.joint_acc")
+        return (self.joint_vel - rep.qd_prev[: self._nd].T) / self._env.cfg.sim.dt
+
+    @property
     def root_state_w(self) -> torch.Tensor:
         s = self._s
         return torch.cat([s["root_pos"], s["root_quat"], s["root_lin"], s["root_ang"]], 0).T.contiguous()
@@ -144,14 +152,24 @@ class _SensorData:
         substep (contact_sensor.py:341 with the contact solve's impulse / dt), 0 elsewhere.  The force
         itself is not kept by the step (only the flag the task reads: allsteps_env.py:421-425 tests
         ``vector_norm(force_matrix_w) > EPSILON``, which this view answers exactly).  None for the
-        unfiltered two-foot sensor, as in the reference."""
+        unfiltered two-foot sensor, as in the reference.
+
+        With ``cfg.contact_forces`` the real thing: the normal contact force (N, world frame) of each stone on
+        each foot in the env step's last substep, the contact report's impulses / sim.dt summed per (foot,
+        stone) by ``as_contact_forces`` -- the sum whose norm the step tested for the flag."""
         return self._sensor._force_matrix()
 
     @property
-    def net_forces_w(self):
-        raise _native.NativeError(
-            "ContactSensor.data.net_forces_w is not available: the MI355X step keeps the per-stone contact "
-            "flags of each foot (force_matrix_w, flag-valued), not net contact forces (INTEGRATION.md §C3)")
+    def net_forces_w(self) -> torch.Tensor:
+        """(N, B, 3) net normal contact force on each sensor body in the last substep (contact_sensor.py:329-335):
+        stones and self-contacts.  ``cfg.contact_forces`` only; without it the step keeps no forces."""
+        return self._sensor._net_forces()[:, 0]
+
+    @property
+    def net_forces_w_history(self) -> torch.Tensor:
+        """(N, T, B, 3) net forces of the env step's last T = decimation substeps, index 0 the latest (the
+        reference's history_length = 4 at one sensor update per physics step)."""
+        return self._sensor._net_forces()
 
 
 class _FootSensor:
@@ -169,12 +187,71 @@ class _FootSensor:
         if not self._filtered:
             return None
         env = self._env
-        m = env.state["contact_mask"]  # (2, N) int32, bit s = stone s
-        bits = torch.arange(env.num_steps, device=m.device, dtype=torch.int32)
-        f = torch.zeros(env.num_envs, self.num_bodies, env.num_steps, 3, device=m.device)
+        ns = env.cfg.num_steps
+        if env._report is not None:
+            fm, _ = env._report.forces()  # (T, 4, 20, 3, N) impulses
+            return fm[0, self._feet, :ns].permute(3, 0, 1, 2) / env.cfg.sim.dt
+        m = env._contact_masks()  # (feet, N) int32, bit s = stone s
+        bits = torch.arange(ns, device=m.device, dtype=torch.int32)
+        f = torch.zeros(env.num_envs, self.num_bodies, ns, 3, device=m.device)
         for k, foot in enumerate(self._feet):
             f[:, k, :, 2] = ((m[foot].unsqueeze(1) >> bits) & 1).float()
         return f
+
+    def _net_forces(self) -> torch.Tensor:
+        """(N, T, B, 3) net contact forces of the sensor's bodies over the stored substeps."""
+        rep = self._env._report_or_raise("ContactSensor.data.net_forces_w")
+        _, net = rep.forces()  # (T, bodies, 3, N) impulses
+        return net[:, [rep.foot_body[f] for f in self._feet]].permute(3, 0, 1, 2) / self._env.cfg.sim.dt
+
+
+class _ContactReport:
+    """The opt-in contact report of an env (``cfg.contact_forces``; include/allsteps.h ABI 6): the device buffers
+    k_step fills for the last ``depth`` substeps of every step, and the dense sums ``as_contact_forces`` makes of
+    them, launched on the env's stream at most once per step however many views are read."""
+
+    def __init__(self, env, depth: int):
+        n, dev = env.num_envs, env._device
+        self._env, self.depth = env, depth
+        self.count = torch.zeros(depth, n, dtype=torch.int32, device=dev)
+        self.records = torch.zeros(depth, _native.REPORT_WORDS, _native.MAXC, n, dtype=torch.int32, device=dev)
+        self.qd_prev = torch.zeros(21, n, dtype=torch.float32, device=dev)
+        env._native.set_contact_report(depth, self.count, self.records, self.qd_prev)
+        m = env.model
+        self._table = _native.make_body_table(m)
+        nb, ng = int(m["num_bodies"]), int(m["num_geoms"])
+        body_link = [int(x) for x in m["body_link"][:nb]]
+        # sensor foot -> the body its geoms' link carries
+        self.foot_body = {int(m["geom_foot"][g]): body_link.index(int(m["geom_link"][g])) for g in range(ng)
+                          if int(m["geom_foot"][g]) >= 0}
+        self._matrix = torch.empty(depth, _native.REPORT_FEET, _native.NUM_STONES, 3, n, device=dev)
+        self._net = torch.empty(depth, nb, 3, n, device=dev)
+        self._stamp = None
+
+    def forces(self):
+        """(force matrix (T, 4, 20, 3, N), net (T, bodies, 3, N)) impulses in N s of the last step."""
+        env = self._env
+        stamp = (env.common_step_counter, env._sim_step_counter, env._launches)
+        if stamp != self._stamp:
+            env._native.contact_forces(self._table, self._matrix, self._net, stream=env._stream())
+            self._stamp = stamp
+        return self._matrix, self._net
+
+
+def _make_report(env, contact_forces):
+    """The env's _ContactReport when cfg.contact_forces (or the constructor's override) asks for one."""
+    on = bool(getattr(env.cfg, "contact_forces", False)) if contact_forces is None else bool(contact_forces)
+    env._launches = 0  # launches that change the report (the views' cache key beside the step counters)
+    return _ContactReport(env, int(env.cfg.decimation)) if on else None
+
+
+def _report_or_raise(env, what: str) -> "_ContactReport":
+    if env._report is None:
+        raise _native.NativeError(
+            f"{what} is not available: the MI355X step keeps the per-stone contact flags of each foot "
+            f"(force_matrix_w, flag-valued), not contact forces or joint accelerations, unless the env is built "
+            f"with cfg.contact_forces = True (INTEGRATION.md §C3)")
+    return env._report
 
 
 class _RobotView:
@@ -208,7 +285,7 @@ class AllstepsEnv(DirectRLEnv):
     cfg: AllstepsEnvCfg
 
     def __init__(self, cfg: AllstepsEnvCfg | None = None, render_mode: str | None = None, *,
-                 env_id_offset: int = 0, model: dict | None = None, **kwargs):
+                 env_id_offset: int = 0, model: dict | None = None, contact_forces: bool | None = None, **kwargs):
         cfg = cfg if cfg is not None else AllstepsEnvCfg()
         super().__init__(cfg, render_mode, **kwargs)
         if self._device.type != "cuda" or not torch.cuda.is_available():
@@ -244,6 +321,8 @@ class AllstepsEnv(DirectRLEnv):
                                              self.env_id_offset)
             # footsteps generated once at init (allsteps_env.py:71), curriculum level 0 by default
             self._native.generate_stones(int(cfg.initial_stone_curriculum), stream=self._stream())
+            # the opt-in contact report (cfg.contact_forces): real contact forces and joint_acc views
+            self._report = _make_report(self, contact_forces)
         # ---- DirectRLEnv buffers (direct_rl_env.py:179-185)
         self.reset_terminated = torch.zeros(n, dtype=torch.bool, device=dev)
         self.reset_time_outs = torch.zeros(n, dtype=torch.bool, device=dev)
@@ -320,6 +399,11 @@ class AllstepsEnv(DirectRLEnv):
         idx = [self.state[k].long() for k in ("prev", "idx", "next")]
         return torch.stack([sp[ar, i] for i in idx], 1)
 
+    _report_or_raise = _report_or_raise
+
+    def _contact_masks(self) -> torch.Tensor:
+        return self.state["contact_mask"]
+
     # ------------------------------------------------------------------ native backend
     def _stream(self):
         return torch.cuda.current_stream(self._device).cuda_stream
@@ -365,6 +449,7 @@ class AllstepsEnv(DirectRLEnv):
         rew = torch.empty(self.num_envs, device=self._device)
         self._native.step(a, obs, rew, self.reset_terminated, self.reset_time_outs, reset_draws,
                           stream=self._stream())
+        self._launches += 1
         self._actions = a
         self.obs_buf = {"policy": obs}
         self.reward_buf = rew
@@ -407,6 +492,7 @@ class AllstepsEnv(DirectRLEnv):
         """Physics only (4 substeps, no task logic) -- known-answer tests / profiling."""
         a = action.to(self._device).float().contiguous()
         self._native.physics_step(a, stream=self._stream())
+        self._launches += 1
 
     def generate_foot_steps(self, level: int, draws: torch.Tensor | None = None):
         """_generate_foot_steps_allsteps at `level` for every env (allsteps_env.py:106-174)."""

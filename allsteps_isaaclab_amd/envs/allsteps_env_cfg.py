@@ -68,6 +68,11 @@ class AllstepsEnvCfg:
     # it, allsteps_env.py:492-500).  True = the intended behaviour: a reset env
     # whose target index was past half the stones gets a new course at the current curriculum level.
     regenerate_footsteps: bool = False
+    # The opt-in contact report: with True the step also stores the contacts its solver kept in each of the
+    # last `decimation` substeps, and the env serves real sensor*.data.force_matrix_w / net_forces_w /
+    # net_forces_w_history (contact_sensor.py:329-343, history_length = 4: allsteps_env_cfg.py:119-130) and
+    # robot.data.joint_acc (articulation_data.py:547-556).  False: the step and its outputs as ever.
+    contact_forces: bool = False
 
     # joint gears, cfg/PhysX dof order (allsteps_env_cfg.py:133-155)
     joint_gears: list = field(default_factory=lambda: [

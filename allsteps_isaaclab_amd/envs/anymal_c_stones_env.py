@@ -46,7 +46,8 @@ class AnymalCStonesEnv(DirectRLEnv):
 
     cfg: AnymalCStonesEnvCfg
 
-    def __init__(self, cfg: AnymalCStonesEnvCfg | None = None, render_mode: str | None = None, **kwargs):
+    def __init__(self, cfg: AnymalCStonesEnvCfg | None = None, render_mode: str | None = None, *,
+                 contact_forces: bool | None = None, **kwargs):
         cfg = cfg or AnymalCStonesEnvCfg()
         super().__init__(cfg, render_mode, **kwargs)
         dev = self._device
@@ -76,6 +77,17 @@ class AnymalCStonesEnv(DirectRLEnv):
         self._native.set_actuator(_native.ACT_DC_MOTOR, action_scale=cfg.action_scale,
                                   default_q=self.default_joint_pos.cpu().tolist(), **cfg.actuator())
         self._native.set_quad_task(**cfg.quad_task())
+        from .allsteps_env import _FootSensor, _make_report
+
+        # the opt-in contact report (cfg.contact_forces) and the four-foot contact sensor over it (sensor order
+        # RF, LF, RH, LH; filtered by the stones): flag-valued force_matrix_w without the report, as the walker's
+        self._report = _make_report(self, contact_forces)
+        body_link = [int(x) for x in self.model["body_link"][: int(self.model["num_bodies"])]]
+        ng = int(self.model["num_geoms"])
+        foot_link = {int(f): int(l) for f, l in zip(self.model["geom_foot"][:ng], self.model["geom_link"][:ng])
+                     if int(f) >= 0}
+        self.sensor = _FootSensor(self, [0, 1, 2, 3],
+                                  [self.model["body_names"][body_link.index(foot_link[f])] for f in range(4)], True)
         # articulation.py:1262-1266: mean -+ 0.5 range * factor (data only, as in IsaacLab)
         lo = torch.tensor([self.model["lower"][self.model["cfg_dof_link"][k]] for k in range(self.num_dof)])
         hi = torch.tensor([self.model["upper"][self.model["cfg_dof_link"][k]] for k in range(self.num_dof)])
@@ -102,6 +114,14 @@ class AnymalCStonesEnv(DirectRLEnv):
 
     def _stream(self) -> int:
         return torch.cuda.current_stream(self._device).cuda_stream
+
+    def _report_or_raise(self, what: str):
+        from .allsteps_env import _report_or_raise
+
+        return _report_or_raise(self, what)
+
+    def _contact_masks(self) -> torch.Tensor:
+        return torch.cat([self.state["contact_mask"], self.state["contact_mask_hind"]], dim=0)
 
     @property
     def episode_length_buf(self) -> torch.Tensor:
@@ -152,6 +172,7 @@ class AnymalCStonesEnv(DirectRLEnv):
 
     def _reset_impl(self):
         self._native.quad_reset_all(self.obs_buf, stream=self._stream())
+        self._launches += 1
         self._reset_buf_stale = True
         return {"policy": self.obs_buf}
 
@@ -161,6 +182,7 @@ class AnymalCStonesEnv(DirectRLEnv):
         a = action.to(torch.float32).contiguous()
         self._native.quad_step(a, self.obs_buf, self.reward_buf, self.reset_terminated, self.reset_time_outs,
                                stream=self._stream())
+        self._launches += 1
         self._reset_buf_stale = True
         return {"policy": self.obs_buf}, self.reward_buf, self.reset_terminated, self.reset_time_outs, self.extras
 

@@ -82,6 +82,8 @@ class AnymalCStonesEnvCfg:
     # stones (as Allsteps-v0: allsteps_env_cfg.py:90-97), level-0 line
     num_steps: int = 20
     step_size: tuple = (0.5, 0.8, 0.225)
+    # the opt-in contact report (as AllstepsEnvCfg.contact_forces): real foot forces and joint_acc views
+    contact_forces: bool = False
 
     # the stepping-stone task (authored; include/allsteps.h as_quad_task_t): the ALLSTEPS target
     # machine and reward terms (allsteps_env.py:347-394, 418-457) on four feet

@@ -9,7 +9,10 @@
  *   get_root_transforms / get_root_velocities / get_dof_positions / get_dof_velocities
  *       (articulation_data.py:374-376, 533, 542)                -> state views (as_state_t)
  *   update_articulations_kinematic (articulation_data.py:439)   -> fused FK inside as_step
- *   RigidContactView.get_contact_force_matrix (contact_sensor.py:341) -> contact_mask (as_state_t)
+ *   RigidContactView.get_contact_force_matrix (contact_sensor.py:341) -> contact_mask (as_state_t);
+ *       the forces themselves, get_net_contact_forces (contact_sensor.py:329) and joint_acc
+ *       (articulation_data.py:547-556) from the opt-in contact report (ABI 6: as_set_contact_report,
+ *       as_contact_forces)
  *   set_root_* / set_dof_* on reset (articulation.py:316-341, 400-420, 472-551) -> in-kernel reset
  * and the task code around it (_apply_action, _get_dones, _get_rewards, _reset_idx,
  * _get_observations), fused into two kernels per env step.
@@ -29,7 +32,7 @@
 extern "C" {
 #endif
 
-#define AS_ABI_VERSION 5
+#define AS_ABI_VERSION 6
 #define AS_MAX_LINKS 32
 #define AS_MAX_GEOMS 32
 #define AS_MAX_SELF_PAIRS 256
@@ -295,6 +298,49 @@ typedef struct {
   float com[AS_MAX_BODIES][3];          /* the body's own centre of mass, body frame */
 } as_body_table_t;
 int as_body_state(as_env_t* env, const as_body_table_t* bodies_host, float* out, void* stream);
+
+/* The contact report (ABI 6), off by default: what the reference's ContactSensor reads beyond the flags
+ * (contact_sensor.py:329-343 net_forces_w / force_matrix_w, history_length = 4: allsteps_env_cfg.py:119-130)
+ * and ArticulationData.joint_acc (articulation_data.py:547-556).  With a report set, every launch with
+ * physics (as_step, as_physics_step, as_quad_step) stores for each of its last `depth` substeps the
+ * contacts the solver kept -- those the row budget cut are not in it -- in caller-owned device buffers,
+ * field-major / env-minor and indexed by env id; substep slot 0 is the launch's last substep:
+ *   count   [depth][n]                                     kept contacts
+ *   records [depth][AS_REPORT_WORDS][AS_MAX_CONTACTS][n]   per contact slot c < count (zeros past it):
+ *             words 0..2  lambda_n * n: the normal impulse (N s, world frame) on the robot link `link`, the
+ *                         very floats the contact flags sum; 0 where the normal row was not solved
+ *             words 3..5  the contact point, relative to the root link's origin, world axes
+ *             word  6     the separation (m, < 0: penetration)
+ *             word  7     link | (link2 + 1) << 8 | (stone + 1) << 16 | (foot + 1) << 24, with link2 the
+ *                         second robot link of a self-contact, stone the stone of a stone contact and foot
+ *                         the geom's contact sensor, each -1 when there is none
+ *   qd_prev [AS_ACT_DIM][n]   joint velocities (cfg dof order) at the start of the launch's last substep:
+ *                             joint_acc = (qd - qd_prev) / dt
+ * Launches without physics (as_reset_*, as_task_step) leave the report as it is, and an env that as_step
+ * resets keeps its last substep's records exactly as it keeps its contact_mask; as_quad_step / as_quad_reset_all,
+ * which clear a reset env's masks, clear its counts.
+ * as_set_contact_report is a setup call like as_debug_stamps (not during graph capture): the pointers are
+ * stored and every later launch writes through them, a replayed graph included.  1 <= depth <=
+ * sim.substeps, else AS_ERR_INVALID; report == NULL switches the report off. */
+#define AS_REPORT_WORDS 8
+#define AS_REPORT_FEET 4   /* contact sensors 0..3 (as_model_t geom_foot) */
+typedef struct {
+  int32_t depth;
+  int32_t* count;
+  uint32_t* records;
+  float* qd_prev;
+} as_contact_report_t;
+int as_set_contact_report(as_env_t* env, const as_contact_report_t* report);
+/* Dense, zero-filled sums over the report as it stands (one launch of k_contact_forces on `stream`, never
+ * part of as_step; no float atomics: every entry is one thread's sum over the env's records in ascending
+ * slot order, from +0 with plain adds -- the contact flags' arithmetic):
+ *   force_matrix_out [depth][AS_REPORT_FEET][AS_NUM_STONES][3][n]  impulse of stone s on sensor foot f
+ *   net_out          [depth][num_bodies][3][n]  net contact impulse on each body of `bodies_host`: + the
+ *                    records whose link is the body's link, - those whose link2 is (a self-contact's second
+ *                    body takes the opposite impulse; a stone contact counts for its robot body only)
+ * Divide by sim.dt for forces.  AS_ERR_INVALID when no report is set or an argument is NULL. */
+int as_contact_forces(as_env_t* env, const as_body_table_t* bodies_host, float* force_matrix_out, float* net_out,
+                      void* stream);
 
 /* The H^-1 sweep plan for a model (round 6, ABI 5; no device needed).  The step kernel sweeps the
  * padded joint-space inertia last block first and, for the trees it is compiled for (the walker, the
