@@ -26,7 +26,7 @@ EXPORTED_SYMBOLS = [
     "as_set_seed", "as_profile", "as_profile_read", "as_debug_stamps", "as_reset_mask", "as_set_graph_safe",
     "as_profile_sampled", "as_hbm_copy", "as_set_actuator", "as_set_quad_task", "as_quad_step", "as_quad_reset_all",
     "as_build_id", "as_step_counters_host", "as_body_state", "as_sweep_plan", "as_set_contact_report",
-    "as_contact_forces",
+    "as_contact_forces", "as_noise_actions", "as_noise_post",
 ]
 MAXB = 32  # AS_MAX_BODIES
 MAXC = 10  # AS_MAX_CONTACTS
@@ -49,6 +49,44 @@ class AsBodyTable(C.Structure):
 class AsContactReport(C.Structure):
     """as_contact_report_t (include/allsteps.h): caller-owned device buffers of the opt-in contact report."""
     _fields_ = [("depth", C.c_int32), ("count", C.c_void_p), ("records", C.c_void_p), ("qd_prev", C.c_void_p)]
+
+
+class AsNoiseModel(C.Structure):
+    """as_noise_model_t (include/allsteps.h): a noise term, its parameter vectors and the optional per-env bias."""
+    _fields_ = [("kind", C.c_int32), ("op", C.c_int32), ("p0", C.c_void_p), ("p1", C.c_void_p),
+                ("bias_kind", C.c_int32), ("bias_op", C.c_int32), ("bias_p0", C.c_float), ("bias_p1", C.c_float),
+                ("bias", C.c_void_p)]
+
+
+NOISE_NONE, NOISE_CONSTANT, NOISE_UNIFORM, NOISE_GAUSSIAN = 0, 1, 2, 3  # AS_NOISE_*
+NOISE_OPS = {"add": 0, "scale": 1, "abs": 2}  # AS_NOISE_ADD / SCALE / ABS
+NOISE_MAX_COLS = 256
+# Philox tags of the noise streams (csrc/allsteps_noise.h): action term, observation term, action bias,
+# observation bias
+NOISE_TAGS = (0x4E416374, 0x4E4F6273, 0x4E416269, 0x4E4F6269)
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def noise_actions(model: AsNoiseModel, src, out, t, draws=None, seed: int = 0, env_offset: int = 0, stream=None):
+    """as_noise_actions: out (n, cols) = model(src), on `stream`; draws (n, cols) injected or None (Philox)."""
+    n, cols = src.shape
+    check(load().as_noise_actions(C.byref(model), src.data_ptr(), out.data_ptr(), n, cols, t.data_ptr(), _ptr(draws),
+                                  seed & 0xFFFFFFFFFFFFFFFF, env_offset, stream), "as_noise_actions")
+
+
+def noise_post(action_model, obs_model, obs, t, reset=None, reset2=None, obs_draws=None, action_bias_draws=None,
+               obs_bias_draws=None, seed: int = 0, env_offset: int = 0, stream=None):
+    """as_noise_post: re-draw the biases of the envs in reset | reset2 (None: all), noise obs (n, cols) in
+    place (None: skip), advance t (n,)."""
+    n = t.shape[0]
+    cols = 0 if obs is None else obs.shape[1]
+    check(load().as_noise_post(None if action_model is None else C.byref(action_model),
+                               None if obs_model is None else C.byref(obs_model), _ptr(obs), n, cols, t.data_ptr(),
+                               _ptr(reset), _ptr(reset2), _ptr(obs_draws), _ptr(action_bias_draws),
+                               _ptr(obs_bias_draws), seed & 0xFFFFFFFFFFFFFFFF, env_offset, stream), "as_noise_post")
 
 
 def unpack_report_ids(w):
@@ -218,6 +256,8 @@ def load() -> C.CDLL:
     L.as_sweep_plan.argtypes = [V, C.POINTER(C.c_uint64)]
     L.as_set_contact_report.argtypes = [V, V]
     L.as_contact_forces.argtypes = [V, V, V, V, V]
+    L.as_noise_actions.argtypes = [V, V, V, I32, I32, V, V, U64, I64, V]
+    L.as_noise_post.argtypes = [V, V, V, I32, I32, V, V, V, V, V, V, U64, I64, V]
     L.as_last_error.restype = C.c_char_p
     L.as_build_id.restype = C.c_char_p
     for name in EXPORTED_SYMBOLS:

@@ -10,6 +10,7 @@
 
 #include "../../include/allsteps.h"
 #include "allsteps_kernels.h"
+#include "allsteps_noise.h"
 
 namespace {
 
@@ -524,6 +525,95 @@ int as_contact_forces(as_env_t* env, const as_body_table_t* bodies_host, float* 
   a.net = net_out;
   a.num_bodies = b.num_bodies;
   HIP_TRY(as::launch_contact_forces(a, reinterpret_cast<hipStream_t>(stream)));
+  return AS_OK;
+}
+
+// as_noise_*: a model's ranges and pointers.  `what` names the call and the model in the message.
+static bool noise_model_ok(const as_noise_model_t& m, const std::string& what, std::string& err) {
+  if (m.kind < AS_NOISE_CONSTANT || m.kind > AS_NOISE_GAUSSIAN)
+    err = what + ": kind " + std::to_string(m.kind) + " outside AS_NOISE_CONSTANT .. AS_NOISE_GAUSSIAN";
+  else if (m.op < AS_NOISE_ADD || m.op > AS_NOISE_ABS)
+    err = what + ": op " + std::to_string(m.op) + " outside AS_NOISE_ADD .. AS_NOISE_ABS";
+  else if (!m.p0 || (m.kind != AS_NOISE_CONSTANT && !m.p1))
+    err = what + ": null parameter vector (p0 / p1)";
+  else if (m.bias_kind < AS_NOISE_NONE || m.bias_kind > AS_NOISE_GAUSSIAN)
+    err = what + ": bias_kind " + std::to_string(m.bias_kind) + " outside AS_NOISE_NONE .. AS_NOISE_GAUSSIAN";
+  else if (m.bias_kind != AS_NOISE_NONE && (m.bias_op < AS_NOISE_ADD || m.bias_op > AS_NOISE_ABS))
+    err = what + ": bias_op " + std::to_string(m.bias_op) + " outside AS_NOISE_ADD .. AS_NOISE_ABS";
+  else if (m.bias_kind != AS_NOISE_NONE && !m.bias)
+    err = what + ": null bias vector with a bias term";
+  else
+    return true;
+  return false;
+}
+
+static bool noise_shape_ok(int32_t n, int32_t cols, const std::string& what, std::string& err) {
+  if (n < 1 || n > AS_MAX_ENVS)
+    err = what + ": n " + std::to_string(n) + " outside [1, AS_MAX_ENVS]";
+  else if (cols < 1 || cols > as::kNoiseMaxCols)
+    err = what + ": cols " + std::to_string(cols) + " outside [1, " + std::to_string(as::kNoiseMaxCols) +
+          "]: a row's column quads must fit one wave";
+  else
+    return true;
+  return false;
+}
+
+static int32_t noise_gshift(int cols) {
+  int32_t s = 0;
+  while ((1 << s) < as::noise_group(cols)) ++s;
+  return s;
+}
+
+int as_noise_actions(const as_noise_model_t* model, const float* in, float* out, int32_t n, int32_t cols,
+                     const uint32_t* t, const float* draws, uint64_t seed, int64_t env_id_offset, void* stream) {
+  if (!model || !in || !out || !t) return fail(AS_ERR_INVALID, "as_noise_actions: null argument (model / in / out / t)");
+  if (in == out) return fail(AS_ERR_INVALID, "as_noise_actions: out must not be in (out of place)");
+  std::string err;
+  if (!noise_shape_ok(n, cols, "as_noise_actions", err) || !noise_model_ok(*model, "as_noise_actions", err))
+    return fail(AS_ERR_INVALID, err);
+  as::NoiseActArgs a{};
+  a.m = *model;
+  a.in = in;
+  a.out = out;
+  a.n = n;
+  a.cols = cols;
+  a.gshift = noise_gshift(cols);
+  a.t = t;
+  a.draws = draws;
+  a.seed = seed;
+  a.env_offset = env_id_offset;
+  HIP_TRY(as::launch_noise_actions(a, reinterpret_cast<hipStream_t>(stream)));
+  return AS_OK;
+}
+
+int as_noise_post(const as_noise_model_t* action_model, const as_noise_model_t* obs_model, float* obs, int32_t n,
+                  int32_t cols, uint32_t* t, const uint8_t* reset, const uint8_t* reset2, const float* obs_draws,
+                  const float* action_bias_draws, const float* obs_bias_draws, uint64_t seed,
+                  int64_t env_id_offset, void* stream) {
+  if (!t) return fail(AS_ERR_INVALID, "as_noise_post: null argument (t)");
+  if (!reset && reset2) return fail(AS_ERR_INVALID, "as_noise_post: reset2 without reset");
+  const bool apply = obs != nullptr && obs_model != nullptr;
+  std::string err;
+  if (!noise_shape_ok(n, apply ? cols : 1, "as_noise_post", err) ||
+      (action_model && !noise_model_ok(*action_model, "as_noise_post: action model", err)) ||
+      (obs_model && !noise_model_ok(*obs_model, "as_noise_post: observation model", err)))
+    return fail(AS_ERR_INVALID, err);
+  as::NoisePostArgs a{};
+  if (action_model) a.act = *action_model;
+  if (obs_model) a.obs = *obs_model;
+  a.data = apply ? obs : nullptr;
+  a.n = n;
+  a.cols = apply ? cols : 0;
+  a.gshift = noise_gshift(a.cols);
+  a.t = t;
+  a.reset = reset;
+  a.reset2 = reset2;
+  a.obs_draws = obs_draws;
+  a.act_bias_draws = action_bias_draws;
+  a.obs_bias_draws = obs_bias_draws;
+  a.seed = seed;
+  a.env_offset = env_id_offset;
+  HIP_TRY(as::launch_noise_post(a, reinterpret_cast<hipStream_t>(stream)));
   return AS_OK;
 }
 

@@ -156,7 +156,36 @@ struct ForcesArgs {
   int32_t link[AS_MAX_BODIES];
 };
 
+// k_noise_actions / k_noise_post (as_noise_actions / as_noise_post, noise_kernels.h).  A model travels by
+// value; kind AS_NOISE_NONE: no model.  gshift = log2(noise_group(cols)): lanes per env
+struct NoiseActArgs {
+  as_noise_model_t m;
+  const float* in;             // [n][cols]
+  float* out;                  // [n][cols]
+  int32_t n, cols, gshift;
+  const uint32_t* t;           // [n] per-env step counter of the noise stream
+  const float* draws;          // [n][cols] injected draws or null: Philox
+  uint64_t seed;
+  int64_t env_offset;
+};
+
+struct NoisePostArgs {
+  as_noise_model_t act, obs;
+  float* data;                 // [n][cols] observations, noised in place, or null: biases and counter only
+  int32_t n, cols, gshift;
+  uint32_t* t;
+  const uint8_t* reset;        // [n] envs whose biases are re-drawn (null: all)
+  const uint8_t* reset2;       // [n] a second mask, ORed with the first, or null
+  const float* obs_draws;      // [n][cols] or null
+  const float* act_bias_draws; // [n] or null
+  const float* obs_bias_draws; // [n] or null
+  uint64_t seed;
+  int64_t env_offset;
+};
+
 bool step_supported_nv(int nv);
+hipError_t launch_noise_actions(const NoiseActArgs& a, hipStream_t stream);
+hipError_t launch_noise_post(const NoisePostArgs& a, hipStream_t stream);
 hipError_t launch_contact_forces(const ForcesArgs& a, hipStream_t stream);
 hipError_t launch_body_state(const BodyArgs& a, hipStream_t stream);
 hipError_t launch_step(const StepArgs& a, int nv, bool sweep_skip, hipStream_t stream);

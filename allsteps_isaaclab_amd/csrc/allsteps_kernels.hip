@@ -457,6 +457,7 @@ __global__ __launch_bounds__(kStepThreads) __attribute__((amdgpu_waves_per_eu(2,
 #include "task_kernels.h"
 #include "body_state_kernel.h"
 #include "contact_forces_kernel.h"
+#include "noise_kernels.h"
 
 namespace as {
 
@@ -510,6 +511,21 @@ hipError_t launch_body_state(const BodyArgs& a, hipStream_t stream) {
 hipError_t launch_contact_forces(const ForcesArgs& a, hipStream_t stream) {
   const int blocks = (a.n + kForcesThreads - 1) / kForcesThreads;
   hipLaunchKernelGGL(k_contact_forces, dim3(blocks, a.depth), dim3(kForcesThreads), 0, stream, a);
+  return hipGetLastError();
+}
+
+// n << gshift threads (n <= AS_MAX_ENVS = 2^24, gshift <= 6: at most 2^22 workgroups)
+hipError_t launch_noise_actions(const NoiseActArgs& a, hipStream_t stream) {
+  const int64_t threads = (int64_t)a.n << a.gshift;
+  hipLaunchKernelGGL(k_noise_actions, dim3((unsigned)((threads + kNoiseThreads - 1) / kNoiseThreads)),
+                     dim3(kNoiseThreads), 0, stream, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_noise_post(const NoisePostArgs& a, hipStream_t stream) {
+  const int64_t threads = (int64_t)a.n << a.gshift;
+  hipLaunchKernelGGL(k_noise_post, dim3((unsigned)((threads + kNoiseThreads - 1) / kNoiseThreads)),
+                     dim3(kNoiseThreads), 0, stream, a);
   return hipGetLastError();
 }
 

@@ -409,6 +409,7 @@ class AllstepsEnv(DirectRLEnv):
         return torch.cuda.current_stream(self._device).cuda_stream
 
     def _reseed(self, seed: int):
+        super()._reseed(seed)
         self._seed_value = int(seed)
         self._native.set_seed(self._seed_value)
 
@@ -423,7 +424,9 @@ class AllstepsEnv(DirectRLEnv):
         gate and second foot-state tick for all envs, as the reference does), then refresh the
         observation buffer.  ``env_ids``: indices, a bool mask, or None (all envs)."""
         if env_ids is None:
-            return self._reset_impl(reset_draws)
+            obs = self._reset_impl(reset_draws)
+            self._noise_reset(None)
+            return obs
         ids = torch.as_tensor(env_ids, device=self._device)
         if ids.dtype == torch.bool:
             if ids.shape != (self.num_envs,):
@@ -438,6 +441,7 @@ class AllstepsEnv(DirectRLEnv):
         obs = torch.empty(self.num_envs, self.cfg.observation_space, device=self._device)
         d = None if reset_draws is None else reset_draws.to(self._device).float().contiguous()
         self._native.reset_mask(mask, obs, d, stream=self._stream())
+        self._noise_reset(mask)
         self.obs_buf = {"policy": obs}
         return self.obs_buf
 
@@ -507,11 +511,12 @@ class AllstepsEnv(DirectRLEnv):
         return int(self._native.counters_host(self._stream())[3])
 
     def get_state(self) -> dict:
-        """Copy of the full SoA state (field -> (rows, N) tensor)."""
-        return {k: v.clone() for k, v in self.state.items()}
+        """Copy of the full SoA state (field -> (rows, N) tensor); with a noise model, also the noise
+        stream's counter and biases (noise_t, noise_action_bias, noise_obs_bias)."""
+        return {**{k: v.clone() for k, v in self.state.items()}, **self._noise_get_state()}
 
     def set_state(self, state: dict):
-        for k, v in state.items():
+        for k, v in self._noise_set_state(state).items():
             self.state[k].copy_(torch.as_tensor(v).to(self.state[k].device, self.state[k].dtype).reshape(
                 self.state[k].shape))
 

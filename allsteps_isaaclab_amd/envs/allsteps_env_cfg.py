@@ -73,6 +73,13 @@ class AllstepsEnvCfg:
     # net_forces_w_history (contact_sensor.py:329-343, history_length = 4: allsteps_env_cfg.py:119-130) and
     # robot.data.joint_acc (articulation_data.py:547-556).  False: the step and its outputs as ever.
     contact_forces: bool = False
+    # Noise models of DirectRLEnvCfg (direct_rl_env_cfg.py:171, 208): a utils.noise NoiseModelCfg /
+    # NoiseModelWithAdditiveBiasCfg (the reference's isaaclab.utils.noise classes) or None.  The action model
+    # perturbs the action before the step, the observation model the policy observation after it, a bias model's
+    # per-env bias is re-drawn for every env that resets -- in HIP kernels around the step (csrc/noise_kernels.h),
+    # one launch more per step for an observation model, two with an action model; None: the step as ever.
+    action_noise_model: object = None
+    observation_noise_model: object = None
 
     # joint gears, cfg/PhysX dof order (allsteps_env_cfg.py:133-155)
     joint_gears: list = field(default_factory=lambda: [

@@ -165,9 +165,10 @@ class AnymalCStonesEnv(DirectRLEnv):
                             target=int(self.state["idx"][env_id]))
 
     def get_state(self) -> dict:
-        return {k: v.clone() for k, v in self.state.items()}
+        return {**{k: v.clone() for k, v in self.state.items()}, **self._noise_get_state()}
 
     def _reseed(self, seed: int):
+        super()._reseed(seed)
         self._native.set_seed(seed)
 
     def _reset_impl(self):

@@ -84,6 +84,9 @@ class AnymalCStonesEnvCfg:
     step_size: tuple = (0.5, 0.8, 0.225)
     # the opt-in contact report (as AllstepsEnvCfg.contact_forces): real foot forces and joint_acc views
     contact_forces: bool = False
+    # noise models (as AllstepsEnvCfg's): a utils.noise NoiseModelCfg / NoiseModelWithAdditiveBiasCfg or None
+    action_noise_model: object = None
+    observation_noise_model: object = None
 
     # the stepping-stone task (authored; include/allsteps.h as_quad_task_t): the ALLSTEPS target
     # machine and reward terms (allsteps_env.py:347-394, 418-457) on four feet

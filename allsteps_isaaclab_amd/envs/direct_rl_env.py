@@ -37,6 +37,12 @@ class DirectRLEnv:
         self._sim_step_counter = 0
         self.extras: dict = {}
         self._configure_gym_env_spaces()
+        # cfg.action_noise_model / cfg.observation_noise_model (direct_rl_env.py:188-195): device state of the
+        # noise kernels, or None -- then step() issues exactly the subclass's launches
+        from .noise import EnvNoise
+
+        self._noise = (EnvNoise(cfg, self.num_envs, self._device, cfg.seed if cfg.seed is not None else 0)
+                       if EnvNoise.wanted(cfg) else None)
 
     # ------------------------------------------------------------------ properties
     @property
@@ -85,15 +91,48 @@ class DirectRLEnv:
             self.seed(seed)
             self._reseed(seed)
         obs = self._reset_impl()
+        self._noise_reset(None)  # the returned observation is not noised (direct_rl_env.py:294)
         return obs, self.extras
 
     def step(self, action: torch.Tensor):
-        """direct_rl_env.py:296-383: one env step (decimation physics substeps inside)."""
+        """direct_rl_env.py:296-383: one env step (decimation physics substeps inside).  With noise models:
+        the action model's output is what the step, ``env.actions`` and the action cost see (:322-323); the
+        envs the step reset get new biases (:578-581) and the policy observation is noised in place (:379-380)."""
         action = action.to(self._device)
         self._sim_step_counter += self.cfg.decimation
+        nz = self._noise
+        if nz is not None and nz.action is not None:
+            action = nz.apply_actions(action, self._noise_offset(), self._noise_stream())
         out = self._step_impl(action)
+        if nz is not None:
+            nz.post(out[0]["policy"], out[2], out[3], self._noise_offset(), self._noise_stream())
         self.common_step_counter += 1
         return out
+
+    # ------------------------------------------------------------------ noise models
+    def _noise_stream(self) -> int:
+        return torch.cuda.current_stream(self._device).cuda_stream
+
+    def _noise_offset(self) -> int:
+        return int(getattr(self, "env_id_offset", 0))  # the shard's first global env id enters the Philox key
+
+    def _noise_reset(self, mask: torch.Tensor | None) -> None:
+        """NoiseModel.reset(env_ids) of both models (direct_rl_env.py:578-581) for the envs of a uint8 mask
+        (None: all) -- the subclass's reset paths call it after their own reset."""
+        if self._noise is not None:
+            self._noise.post(None, mask, None, self._noise_offset(), self._noise_stream())
+
+    def _noise_get_state(self) -> dict:
+        """The noise stream's counter and biases for get_state (no keys without a model)."""
+        return {} if self._noise is None else self._noise.get_state()
+
+    def _noise_set_state(self, state: dict) -> dict:
+        """Load the noise keys of a set_state dict; returns the dict without them."""
+        from .noise import EnvNoise
+
+        if self._noise is not None:
+            self._noise.set_state(state)
+        return {k: v for k, v in state.items() if k not in EnvNoise.STATE_KEYS}
 
     @staticmethod
     def seed(seed: int = -1) -> int:
@@ -132,7 +171,9 @@ class DirectRLEnv:
 
     # ------------------------------------------------------------------ subclass hooks
     def _reseed(self, seed: int):
-        pass
+        """Re-seed the device streams (subclasses extend it): here the noise models' Philox key."""
+        if self._noise is not None:
+            self._noise.seed = int(seed)
 
     def _reset_impl(self):
         raise NotImplementedError

@@ -342,6 +342,42 @@ int as_set_contact_report(as_env_t* env, const as_contact_report_t* report);
 int as_contact_forces(as_env_t* env, const as_body_table_t* bodies_host, float* force_matrix_out, float* net_out,
                       void* stream);
 
+/* Noise models, off by default: DirectRLEnv.step's cfg.action_noise_model / cfg.observation_noise_model
+ * (direct_rl_env.py:322-323, 379-380, 578-581; isaaclab/utils/noise/noise_model.py).  Stateless entry points
+ * over caller-owned device buffers -- no as_env_t: the env step itself is unchanged, the caller launches
+ * as_noise_actions before it and as_noise_post after it on the same stream (envs/direct_rl_env.py).  A model
+ * is a term (kind, op, two parameter vectors [cols]) and an optional per-env additive bias re-drawn from a
+ * second, scalar term for the envs that reset (NoiseModelWithAdditiveBias).  Parameters p0 / p1: the bias
+ * / unused (constant), n_min / n_max - n_min (uniform), mean / std (gaussian).  Formulas, Philox stream
+ * layout (seed, env_id_offset + e, t[e], column quad, tag) and the float32 rounding order that reproduces
+ * torch's bits from the same draws: csrc/allsteps_noise.h.  t [n] is the per-env step counter of the stream,
+ * advanced by as_noise_post only; zero it at construction and keep it with the state.  Both calls are
+ * graph-safe: nothing per call comes from the host but the pointers. */
+enum { AS_NOISE_NONE = 0, AS_NOISE_CONSTANT = 1, AS_NOISE_UNIFORM = 2, AS_NOISE_GAUSSIAN = 3 };
+enum { AS_NOISE_ADD = 0, AS_NOISE_SCALE = 1, AS_NOISE_ABS = 2 };
+typedef struct {
+  int32_t kind, op;           /* the term: AS_NOISE_CONSTANT / UNIFORM / GAUSSIAN, AS_NOISE_ADD / SCALE / ABS */
+  const float* p0;            /* [cols] */
+  const float* p1;            /* [cols] (not read by the constant term: may be NULL) */
+  int32_t bias_kind, bias_op; /* the bias term, AS_NOISE_NONE: a plain NoiseModel without a bias */
+  float bias_p0, bias_p1;
+  float* bias;                /* [n] the per-env bias (bias_kind != AS_NOISE_NONE) */
+} as_noise_model_t;
+/* out [n][cols] = model(in [n][cols]), out of place (in is never written; out != in).  draws: NULL (Philox,
+ * the action-term stream at t[e]) or [n][cols] injected draws -- uniforms in [0, 1) or unit normals as the
+ * kind needs.  1 <= cols <= 256. */
+int as_noise_actions(const as_noise_model_t* model, const float* in, float* out, int32_t n, int32_t cols,
+                     const uint32_t* t, const float* draws, uint64_t seed, int64_t env_id_offset, void* stream);
+/* After the step, in one launch: for the envs with reset[e] | reset2[e] != 0 ([n] uint8 each; reset2 may be
+ * NULL; reset NULL: every env) re-draw the bias of action_model and of obs_model (either may be NULL or have
+ * no bias); then obs [n][cols] = obs_model(obs) in place with the biases as they now stand; then t[e] += 1.
+ * obs NULL (cols ignored) serves reset() and _reset_idx: bias re-draw and counter only.  obs_draws [n][cols],
+ * action_bias_draws [n], obs_bias_draws [n]: injected draws or NULL (Philox streams at t[e]). */
+int as_noise_post(const as_noise_model_t* action_model, const as_noise_model_t* obs_model, float* obs, int32_t n,
+                  int32_t cols, uint32_t* t, const uint8_t* reset, const uint8_t* reset2, const float* obs_draws,
+                  const float* action_bias_draws, const float* obs_bias_draws, uint64_t seed,
+                  int64_t env_id_offset, void* stream);
+
 /* The H^-1 sweep plan for a model (round 6, ABI 5; no device needed).  The step kernel sweeps the
  * padded joint-space inertia last block first and, for the trees it is compiled for (the walker, the
  * C5 quadruped), skips the column quads in which the pivot rows are structurally zero -- an exact
