@@ -412,8 +412,8 @@ class NativeEnv:
         for name, _, _ in STATE_LAYOUT:
             setattr(S, name, state[name].data_ptr())
         S.curriculum = state["curriculum"].data_ptr()
-        S.contact_mask_hind = state["contact_mask_hind"].data_ptr() if "contact_mask_hind" in state else None
-        S.feet = state["feet"].data_ptr() if "feet" in state else None
+        S.contact_mask_hind = _ptr(state.get("contact_mask_hind"))
+        S.feet = _ptr(state.get("feet"))
         self._state = S
         h = C.c_void_p()
         check(self.L.as_create(n, C.byref(self._model), C.byref(self._sim), C.byref(self._task), C.byref(S),
@@ -433,13 +433,11 @@ class NativeEnv:
 
     def step(self, actions, obs, rew, term, trunc, reset_draws=None, stream=None):
         check(self.L.as_step(self.h, actions.data_ptr(), obs.data_ptr(), rew.data_ptr(), term.data_ptr(),
-                             trunc.data_ptr(), reset_draws.data_ptr() if reset_draws is not None else None,
-                             stream), "as_step")
+                             trunc.data_ptr(), _ptr(reset_draws), stream), "as_step")
 
     def task_step(self, actions, obs, rew, term, trunc, reset_draws=None, stream=None):
         check(self.L.as_task_step(self.h, actions.data_ptr(), obs.data_ptr(), rew.data_ptr(), term.data_ptr(),
-                                  trunc.data_ptr(), reset_draws.data_ptr() if reset_draws is not None else None,
-                                  stream), "as_task_step")
+                                  trunc.data_ptr(), _ptr(reset_draws), stream), "as_task_step")
 
     def set_seed(self, seed: int):
         check(self.L.as_set_seed(self.h, seed & 0xFFFFFFFFFFFFFFFF), "as_set_seed")
@@ -448,13 +446,10 @@ class NativeEnv:
         check(self.L.as_set_graph_safe(self.h, int(bool(on))), "as_set_graph_safe")
 
     def reset_all(self, obs, reset_draws=None, stream=None):
-        check(self.L.as_reset_all(self.h, obs.data_ptr(),
-                                  reset_draws.data_ptr() if reset_draws is not None else None, stream),
-              "as_reset_all")
+        check(self.L.as_reset_all(self.h, obs.data_ptr(), _ptr(reset_draws), stream), "as_reset_all")
 
     def reset_mask(self, mask, obs, reset_draws=None, stream=None):
-        check(self.L.as_reset_mask(self.h, mask.data_ptr(), obs.data_ptr(),
-                                   reset_draws.data_ptr() if reset_draws is not None else None, stream),
+        check(self.L.as_reset_mask(self.h, mask.data_ptr(), obs.data_ptr(), _ptr(reset_draws), stream),
               "as_reset_mask")
 
     def physics_step(self, actions, stream=None):
@@ -473,7 +468,7 @@ class NativeEnv:
             return
         R = AsContactReport()
         R.depth = int(depth)
-        R.count, R.records, R.qd_prev = (None if t is None else t.data_ptr() for t in (count, records, qd_prev))
+        R.count, R.records, R.qd_prev = (_ptr(t) for t in (count, records, qd_prev))
         check(self.L.as_set_contact_report(self.h, C.byref(R)), "as_set_contact_report")
         self._report = (R, count, records, qd_prev)
 
@@ -481,8 +476,7 @@ class NativeEnv:
         """as_contact_forces: force_matrix_out fp32 [depth][REPORT_FEET][NUM_STONES][3][n], net_out fp32
         [depth][num_bodies][3][n] (impulses, N s) from the report as it stands."""
         check(self.L.as_contact_forces(self.h, C.byref(table) if table is not None else None,
-                                       None if force_matrix_out is None else force_matrix_out.data_ptr(),
-                                       None if net_out is None else net_out.data_ptr(), stream), "as_contact_forces")
+                                       _ptr(force_matrix_out), _ptr(net_out), stream), "as_contact_forces")
 
     def set_actuator(self, mode: int, action_scale: float = 0.0, default_q=(), stiffness: float = 0.0,
                      damping: float = 0.0, saturation_effort: float = 0.0, effort_limit: float = 0.0,
@@ -513,8 +507,7 @@ class NativeEnv:
         check(self.L.as_quad_reset_all(self.h, obs.data_ptr(), stream), "as_quad_reset_all")
 
     def generate_stones(self, level: int, draws=None, stream=None):
-        check(self.L.as_generate_stones(self.h, level, draws.data_ptr() if draws is not None else None, stream),
-              "as_generate_stones")
+        check(self.L.as_generate_stones(self.h, level, _ptr(draws), stream), "as_generate_stones")
 
     def profile_sampled(self, max_records: int, stride: int):
         check(self.L.as_profile_sampled(self.h, max_records, stride), "as_profile_sampled")
@@ -528,7 +521,7 @@ class NativeEnv:
         return a.value, b.value, k.value
 
     def debug_stamps(self, buf):
-        check(self.L.as_debug_stamps(self.h, None if buf is None else buf.data_ptr()), "as_debug_stamps")
+        check(self.L.as_debug_stamps(self.h, _ptr(buf)), "as_debug_stamps")
 
     def counters_host(self, stream=None) -> list:
         """The last step's counter words [any reset, target-index sum, regen level, contacts dropped]

@@ -12,35 +12,17 @@ CPU fallback: without the HIP library or a gfx950 device the constructor raises 
 
 from __future__ import annotations
 
-import numpy as np
 import torch
 
 from .. import _native
 from ..model import ANYMAL_C_JSON, load_model
 from .anymal_c_stones_env_cfg import AnymalCStonesEnvCfg
-from .direct_rl_env import DirectRLEnv
+from .native_env import NativeDirectEnv
+from .quadruped import level0_stones, stand_pose
+from .views import _FootSensor, _RobotView
 
 
-def stand_pose(dof_names: list[str], init: dict) -> np.ndarray:
-    """Default joint positions in the model's cfg DOF order from ANYMAL_C_CFG's regex-style table
-    (HAA, {F,H}_HFE, {F,H}_KFE)."""
-    q = np.zeros(len(dof_names), np.float32)
-    for k, name in enumerate(dof_names):
-        leg, joint = name.split("_")
-        q[k] = init["HAA"] if joint == "HAA" else init[f"{leg[1]}_{joint}"]
-    return q
-
-
-def level0_stones(n: int, num_steps: int = 20) -> np.ndarray:
-    """steps_pos of curriculum level 0 ([3 * num_steps][n]): x = 0.75 k, y = 0, z = 0.75 k cos(pi/2)."""
-    st = np.zeros((3 * num_steps, n), np.float32)
-    for k in range(num_steps):
-        st[3 * k] = 0.75 * k
-        st[3 * k + 2] = np.float32(k * 0.75) * np.cos(np.float32(np.pi / 2), dtype=np.float32)
-    return st
-
-
-class AnymalCStonesEnv(DirectRLEnv):
+class AnymalCStonesEnv(NativeDirectEnv):
     """The C5 task env: ``reset() -> ({"policy": obs}, extras)``, ``step(a) -> ({"policy": obs}, reward,
     terminated, truncated, extras)``; every buffer on the device."""
 
@@ -50,38 +32,22 @@ class AnymalCStonesEnv(DirectRLEnv):
                  contact_forces: bool | None = None, **kwargs):
         cfg = cfg or AnymalCStonesEnvCfg()
         super().__init__(cfg, render_mode, **kwargs)
-        dev = self._device
-        if dev.type != "cuda" or not torch.cuda.is_available():
-            raise _native.NativeError(f"AnymalCStonesEnv runs on the HIP backend only (device={dev}, HIP device "
-                                      f"available: {torch.cuda.is_available()}); there is no CPU fallback")
-        self.model = load_model(ANYMAL_C_JSON)
+        model = load_model(ANYMAL_C_JSON)
         if not cfg.robot.enabled_self_collisions:  # ArticulationRootPropertiesCfg.enabled_self_collisions
-            self.model = dict(self.model, num_self_pairs=0, self_pair=[0] * len(self.model["self_pair"]))
-        n = self.num_envs
-        self.num_dof = self.model["num_hinges"]
+            model = dict(model, num_self_pairs=0, self_pair=[0] * len(model["self_pair"]))
+        self.num_dof = model["num_hinges"]
         if self.num_dof != cfg.action_space:
             raise ValueError(f"model has {self.num_dof} hinges, cfg.action_space = {cfg.action_space}")
-        self.state: dict[str, torch.Tensor] = {}
-        for name, rows, t in _native.STATE_LAYOUT:
-            self.state[name] = torch.zeros((rows, n) if rows > 1 else (n,), device=dev,
-                                           dtype=torch.float32 if t == "f" else torch.int32)
-        self.state["curriculum"] = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.state["contact_mask_hind"] = torch.zeros((2, n), dtype=torch.int32, device=dev)  # sensors RH, LH
-        self.state["feet"] = torch.zeros((8, n), dtype=torch.int32, device=dev)  # per-foot targets | reach counts
+        # the opt-in contact report (cfg.contact_forces) comes with the handle
+        self._init_native(model, hind=True, feet=True, contact_forces=contact_forces)
+        n, dev = self.num_envs, self._device
         self.state["stones"][:] = torch.as_tensor(level0_stones(n, cfg.num_steps), device=dev)
-        with torch.cuda.device(dev):
-            self._native = _native.NativeEnv(n, self.model, cfg, self.state, int(cfg.seed or 0),
-                                             dev.index if dev.index is not None else torch.cuda.current_device())
-        self.default_joint_pos = torch.as_tensor(stand_pose(self.model["dof_names"], cfg.robot.init_joint_pos),
-                                                 device=dev)
+        self.default_joint_pos = torch.as_tensor(stand_pose(model["dof_names"], cfg.robot.init_joint_pos), device=dev)
         self._native.set_actuator(_native.ACT_DC_MOTOR, action_scale=cfg.action_scale,
                                   default_q=self.default_joint_pos.cpu().tolist(), **cfg.actuator())
         self._native.set_quad_task(**cfg.quad_task())
-        from .allsteps_env import _FootSensor, _make_report
-
-        # the opt-in contact report (cfg.contact_forces) and the four-foot contact sensor over it (sensor order
-        # RF, LF, RH, LH; filtered by the stones): flag-valued force_matrix_w without the report, as the walker's
-        self._report = _make_report(self, contact_forces)
+        # the four-foot contact sensor (sensor order RF, LF, RH, LH; filtered by the stones): flag-valued
+        # force_matrix_w without the contact report, as the walker's
         body_link = [int(x) for x in self.model["body_link"][: int(self.model["num_bodies"])]]
         ng = int(self.model["num_geoms"])
         foot_link = {int(f): int(l) for f, l in zip(self.model["geom_foot"][:ng], self.model["geom_link"][:ng])
@@ -107,25 +73,8 @@ class AnymalCStonesEnv(DirectRLEnv):
         self.extras = {}
         self._native.quad_reset_all(self.obs_buf, stream=self._stream())
         # the ArticulationData views (ring 1 zero-copy, ring 2 -- the 13 MJCF bodies -- by as_body_state on
-        # demand), as the walker's env serves them (envs/allsteps_env.py)
-        from .allsteps_env import _RobotView
-
-        self.robot = _RobotView(self)
-
-    def _stream(self) -> int:
-        return torch.cuda.current_stream(self._device).cuda_stream
-
-    def _report_or_raise(self, what: str):
-        from .allsteps_env import _report_or_raise
-
-        return _report_or_raise(self, what)
-
-    def _contact_masks(self) -> torch.Tensor:
-        return torch.cat([self.state["contact_mask"], self.state["contact_mask_hind"]], dim=0)
-
-    @property
-    def episode_length_buf(self) -> torch.Tensor:
-        return self.state["ep_len"]
+        # demand), as the walker's env serves them (envs/views.py)
+        self.robot = _RobotView(self, default_joint_pos=self.default_joint_pos)
 
     @property
     def target_index(self) -> torch.Tensor:
@@ -154,22 +103,7 @@ class AnymalCStonesEnv(DirectRLEnv):
     @property
     def contact_mask(self) -> torch.Tensor:
         """(N, 4) stone bitmasks of the four sensor feet (RF, LF, RH, LH) in the last substep."""
-        return torch.cat([self.state["contact_mask"], self.state["contact_mask_hind"]], dim=0).T
-
-    def _render_rgb(self, env_id: int):
-        from .render import render_frame
-
-        st = {k: self.state[k][..., env_id].detach().cpu().numpy() for k in ("root_pos", "root_quat", "q", "stones")}
-        half = [0.5 * v for v in self.cfg.step_size]
-        return render_frame(self.model, st["root_pos"], st["root_quat"], st["q"], st["stones"].reshape(-1, 3), half,
-                            target=int(self.state["idx"][env_id]))
-
-    def get_state(self) -> dict:
-        return {**{k: v.clone() for k, v in self.state.items()}, **self._noise_get_state()}
-
-    def _reseed(self, seed: int):
-        super()._reseed(seed)
-        self._native.set_seed(seed)
+        return self._contact_masks().T
 
     def _reset_impl(self):
         self._native.quad_reset_all(self.obs_buf, stream=self._stream())
@@ -186,9 +120,3 @@ class AnymalCStonesEnv(DirectRLEnv):
         self._launches += 1
         self._reset_buf_stale = True
         return {"policy": self.obs_buf}, self.reward_buf, self.reset_terminated, self.reset_time_outs, self.extras
-
-    def close(self):
-        if getattr(self, "_native", None) is not None:
-            self._native.close()
-            self._native = None
-        super().close()

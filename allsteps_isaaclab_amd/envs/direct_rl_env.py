@@ -23,6 +23,7 @@ class DirectRLEnv:
 
     is_vector_env = True
     metadata: dict = {"render_modes": [None, "rgb_array"], "isaac_sim_version": None}
+    env_id_offset = 0  # a shard's first global env id (it enters the noise models' Philox key)
 
     def __init__(self, cfg, render_mode: str | None = None, **kwargs):
         self.cfg = cfg
@@ -114,7 +115,7 @@ class DirectRLEnv:
         return torch.cuda.current_stream(self._device).cuda_stream
 
     def _noise_offset(self) -> int:
-        return int(getattr(self, "env_id_offset", 0))  # the shard's first global env id enters the Philox key
+        return self.env_id_offset
 
     def _noise_reset(self, mask: torch.Tensor | None) -> None:
         """NoiseModel.reset(env_ids) of both models (direct_rl_env.py:578-581) for the envs of a uint8 mask

@@ -1,0 +1,84 @@
+"""``NativeDirectEnv`` -- what the direct-workflow envs on the HIP step library share: the SoA state, the
+``NativeEnv`` handle over it, the opt-in contact report, state save / restore, rendering and shutdown.  The task
+envs (``AllstepsEnv``, ``AnymalCStonesEnv``) add their own ``_step_impl`` / ``_reset_impl`` and task buffers."""
+
+from __future__ import annotations
+
+import torch
+
+from .. import _native
+from .direct_rl_env import DirectRLEnv
+from .state import alloc_state
+from .views import _ContactReport
+
+
+class NativeDirectEnv(DirectRLEnv):
+    _native = None  # the NativeEnv handle: None before _init_native and after close
+
+    def _init_native(self, model: dict, *, hind: bool = False, feet: bool = False, env_id_offset: int = 0,
+                     contact_forces: bool | None = None) -> None:
+        """After ``DirectRLEnv.__init__``: the zeroed device state (``alloc_state(n, device, hind=, feet=)``), the
+        handle over it, seeded with ``cfg.seed``, and the contact report when ``cfg.contact_forces`` (or the
+        constructor's override ``contact_forces``) asks for one.  Env-specific initial values are the caller's."""
+        dev = self._device
+        if dev.type != "cuda" or not torch.cuda.is_available():
+            raise _native.NativeError(f"{type(self).__name__} runs on the HIP backend only (device={dev}, HIP device "
+                                      f"available: {torch.cuda.is_available()}); there is no CPU fallback")
+        self.model = model
+        self.state = alloc_state(self.num_envs, dev, hind=hind, feet=feet)  # SoA, resident in HBM ([field][env])
+        self.env_id_offset = int(env_id_offset)
+        with torch.cuda.device(dev):
+            self._native = _native.NativeEnv(self.num_envs, model, self.cfg, self.state, int(self.cfg.seed or 0),
+                                             dev.index if dev.index is not None else torch.cuda.current_device(),
+                                             self.env_id_offset)
+            self._launches = 0  # launches that change the report (the views' cache key beside the step counters)
+            on = self.cfg.contact_forces if contact_forces is None else contact_forces
+            self._report = _ContactReport(self, int(self.cfg.decimation)) if on else None
+
+    episode_length_buf = property(lambda self: self.state["ep_len"])
+
+    def _stream(self) -> int:
+        return torch.cuda.current_stream(self._device).cuda_stream
+
+    _noise_stream = _stream
+
+    def _report_or_raise(self, what: str) -> _ContactReport:
+        if self._report is None:
+            raise _native.NativeError(
+                f"{what} is not available: the MI355X step keeps the per-stone contact flags of each foot "
+                f"(force_matrix_w, flag-valued), not contact forces or joint accelerations, unless the env is built "
+                f"with cfg.contact_forces = True (INTEGRATION.md §C3)")
+        return self._report
+
+    def _contact_masks(self) -> torch.Tensor:
+        """(feet, N) stone bitmasks of the sensor feet in the last substep: two rows, four with the hind pair."""
+        s = self.state
+        return torch.cat([s["contact_mask"], s["contact_mask_hind"]]) if "contact_mask_hind" in s else s["contact_mask"]
+
+    def _render_rgb(self, env_id: int):
+        from .render import render_frame
+
+        st = {k: self.state[k][..., env_id].detach().cpu().numpy() for k in ("root_pos", "root_quat", "q", "stones")}
+        half = [0.5 * v for v in self.cfg.step_size]
+        return render_frame(self.model, st["root_pos"], st["root_quat"], st["q"], st["stones"].reshape(-1, 3), half,
+                            target=int(self.state["idx"][env_id]))
+
+    def get_state(self) -> dict:
+        """Copy of the full SoA state (field -> (rows, N) tensor); with a noise model, also the noise
+        stream's counter and biases (noise_t, noise_action_bias, noise_obs_bias)."""
+        return {**{k: v.clone() for k, v in self.state.items()}, **self._noise_get_state()}
+
+    def set_state(self, state: dict):
+        for k, v in self._noise_set_state(state).items():
+            self.state[k].copy_(torch.as_tensor(v).to(self.state[k].device, self.state[k].dtype).reshape(
+                self.state[k].shape))
+
+    def _reseed(self, seed: int):
+        super()._reseed(seed)
+        self._native.set_seed(int(seed))
+
+    def close(self):
+        if self._native is not None:
+            self._native.close()
+            self._native = None
+        super().close()

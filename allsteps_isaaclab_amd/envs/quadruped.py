@@ -25,8 +25,7 @@ import torch
 from .. import _native
 from ..model import ANYMAL_C_JSON, load_model
 from .allsteps_env_cfg import AllstepsEnvCfg
-from .anymal_c_stones_env import level0_stones  # noqa: F401  (re-exported for the physics tests)
-from .anymal_c_stones_env import stand_pose as _stand_pose
+from .state import alloc_state
 
 # ANYmal default stance (IsaacLab ANYMAL_C_CFG init_state: HAA 0, front HFE 0.4 / KFE -0.8, hind HFE
 # -0.4 / KFE 0.8), in the model's cfg DOF order
@@ -37,12 +36,29 @@ STAND_ROOT = (0.375, 0.0, 0.1125 + 0.574 + 0.01)
 ACT_SCALE = 80.0  # N m per unit action (1.2 * gear)
 
 
-def stand_pose(dof_names: list[str]) -> np.ndarray:
-    return _stand_pose(dof_names, STAND_Q)
+def stand_pose(dof_names: list[str], init: dict = STAND_Q) -> np.ndarray:
+    """Default joint positions in the model's cfg DOF order from ANYMAL_C_CFG's regex-style table
+    (HAA, {F,H}_HFE, {F,H}_KFE)."""
+    q = np.zeros(len(dof_names), np.float32)
+    for k, name in enumerate(dof_names):
+        leg, joint = name.split("_")
+        q[k] = init["HAA"] if joint == "HAA" else init[f"{leg[1]}_{joint}"]
+    return q
+
+
+def level0_stones(n: int, num_steps: int = 20) -> np.ndarray:
+    """steps_pos of curriculum level 0 ([3 * num_steps][n]): x = 0.75 k, y = 0, z = 0.75 k cos(pi/2)."""
+    st = np.zeros((3 * num_steps, n), np.float32)
+    for k in range(num_steps):
+        st[3 * k] = 0.75 * k
+        st[3 * k + 2] = np.float32(k * 0.75) * np.cos(np.float32(np.pi / 2), dtype=np.float32)
+    return st
 
 
 class QuadrupedStonesEnv:
     """Physics-only vectorised quadruped on stepping stones (HIP, k_step<18>)."""
+
+    _native = None  # the NativeEnv handle: None before construction got to it and after close
 
     def __init__(self, num_envs: int, device: str = "cuda:0", seed: int = 42, cfg: AllstepsEnvCfg | None = None):
         self.device = torch.device(device)
@@ -53,12 +69,7 @@ class QuadrupedStonesEnv:
         self.num_envs = n = int(num_envs)
         self.num_dof = self.model["num_hinges"]
         dev = self.device
-        self.state: dict[str, torch.Tensor] = {}
-        for name, rows, t in _native.STATE_LAYOUT:
-            dt = torch.float32 if t == "f" else torch.int32
-            self.state[name] = torch.zeros((rows, n) if rows > 1 else (n,), dtype=dt, device=dev)
-        self.state["curriculum"] = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.state["contact_mask_hind"] = torch.zeros((2, n), dtype=torch.int32, device=dev)  # sensors RH, LH
+        self.state = alloc_state(n, dev, hind=True)
         with torch.cuda.device(dev):
             self._native = _native.NativeEnv(n, self.model, self.cfg, self.state, seed,
                                              dev.index if dev.index is not None else torch.cuda.current_device())
@@ -101,6 +112,6 @@ class QuadrupedStonesEnv:
         return torch.cat([self.state["contact_mask"], self.state["contact_mask_hind"]], dim=0).T
 
     def close(self) -> None:
-        if getattr(self, "_native", None) is not None:
+        if self._native is not None:
             self._native.close()
             self._native = None

@@ -130,13 +130,10 @@ class GpuPhysics:
 
         from allsteps_isaaclab_amd import _native
         from allsteps_isaaclab_amd.envs.allsteps_env_cfg import AllstepsEnvCfg
+        from allsteps_isaaclab_amd.envs.state import alloc_state
 
         self.n = n
-        self.state = {}
-        for name, rows, t in _native.STATE_LAYOUT:
-            self.state[name] = torch.zeros((rows, n) if rows > 1 else (n,),
-                                           dtype=torch.float32 if t == "f" else torch.int32, device="cuda:0")
-        self.state["curriculum"] = torch.zeros(1, dtype=torch.int32, device="cuda:0")
+        self.state = alloc_state(n, torch.device("cuda:0"))
         self.state["root_quat"][0] = 1.0
         self.native = _native.NativeEnv(n, model, AllstepsEnvCfg(), self.state, seed, 0)
 

@@ -331,3 +331,41 @@ def test_c5_task_gpu_bit_exact_vs_oracle(qorc, oracle_mod, qmodel, n, steps, war
             assert bool(env.reset_buf[:3].all())
     assert total_resets > 0  # robots fall and reset inside the compared steps: the reset path is exercised
     env.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("contact_forces", [False, True])
+def test_c5_set_state_replays_bit_exact(contact_forces):
+    """get_state / set_state hold everything a step depends on: 8 steps replayed from a saved state give the same
+    observations, rewards and dones, and end in the same state, bit for bit (n = 66: a partial last wave)."""
+    from allsteps_isaaclab_amd.envs.anymal_c_stones_env import AnymalCStonesEnv
+
+    n = 66
+    cfg = AnymalCStonesEnvCfg()
+    cfg.scene.num_envs = n
+    env = AnymalCStonesEnv(cfg, contact_forces=contact_forces)
+    env.reset()
+    gen = torch.Generator().manual_seed(11)
+    acts = (torch.rand(16, n, 12, generator=gen) * 2.4 - 1.2).cuda()
+    for t in range(8):
+        env.step(acts[t])
+    saved = env.get_state()
+
+    def run():
+        out = []
+        for t in range(8, 16):
+            obs, rew, term, trunc, _ = env.step(acts[t])
+            out.append([x.clone() for x in (obs["policy"], rew, term, trunc)])
+        return out, env.get_state()
+
+    first, end_first = run()
+    env.set_state(saved)
+    second, end_second = run()
+    for t, (a, b) in enumerate(zip(first, second)):
+        for name, x, y in zip(("obs", "reward", "terminated", "truncated"), a, b):
+            assert torch.equal(x, y), f"step {8 + t}: {name} differs after set_state"
+    assert sorted(end_first) == sorted(end_second) == sorted(saved)
+    for k in end_first:
+        assert torch.equal(end_first[k], end_second[k]), f"final state differs in {k}"
+    assert not all(torch.equal(saved[k], end_first[k]) for k in saved)  # the 8 steps moved the state
+    env.close()
