@@ -26,7 +26,7 @@ EXPORTED_SYMBOLS = [
     "as_set_seed", "as_profile", "as_profile_read", "as_debug_stamps", "as_reset_mask", "as_set_graph_safe",
     "as_profile_sampled", "as_hbm_copy", "as_set_actuator", "as_set_quad_task", "as_quad_step", "as_quad_reset_all",
     "as_build_id", "as_step_counters_host", "as_body_state", "as_sweep_plan", "as_set_contact_report",
-    "as_contact_forces", "as_noise_actions", "as_noise_post",
+    "as_contact_forces", "as_noise_actions", "as_noise_post", "as_events_init", "as_events_interval",
 ]
 MAXB = 32  # AS_MAX_BODIES
 MAXC = 10  # AS_MAX_CONTACTS
@@ -87,6 +87,32 @@ def noise_post(action_model, obs_model, obs, t, reset=None, reset2=None, obs_dra
                                None if obs_model is None else C.byref(obs_model), _ptr(obs), n, cols, t.data_ptr(),
                                _ptr(reset), _ptr(reset2), _ptr(obs_draws), _ptr(action_bias_draws),
                                _ptr(obs_bias_draws), seed & 0xFFFFFFFFFFFFFFFF, env_offset, stream), "as_noise_post")
+
+
+MAX_EVENT_TERMS = 4  # AS_MAX_EVENT_TERMS
+EVENT_TERM_FLOATS = 14  # as_event_term_t: interval_lo, interval_w, vel_lo[6], vel_w[6]
+# Philox tags of the event streams (csrc/allsteps_events.h): interval resamples, pushes
+EVENT_TAGS = (0x45764976, 0x45765075)
+
+
+def events_init(terms, time_left, t, interval_draws=None, seed: int = 0, env_offset: int = 0, stream=None):
+    """as_events_init: time_left (terms, n) = the initial timers, t (n,) = 1.  terms: (terms, 14) float32 device
+    rows of as_event_term_t; interval_draws (terms, n) injected or None (Philox at counter 0)."""
+    k, n = time_left.shape
+    check(load().as_events_init(terms.data_ptr(), k, time_left.data_ptr(), t.data_ptr(), n, _ptr(interval_draws),
+                                seed & 0xFFFFFFFFFFFFFFFF, env_offset, stream), "as_events_init")
+
+
+def events_interval(terms, root_lin, root_ang, time_left, t, dt: float, fired=None, interval_draws=None,
+                    push_draws=None, seed: int = 0, env_offset: int = 0, stream=None):
+    """as_events_interval: one env step of the interval terms on root_lin / root_ang (3, n), time_left
+    (terms, n), t (n,); fired (terms, n) uint8 or None; interval_draws (terms, n), push_draws (terms, 6, n)
+    injected or None (Philox)."""
+    k, n = time_left.shape
+    check(load().as_events_interval(terms.data_ptr(), k, root_lin.data_ptr(), root_ang.data_ptr(),
+                                    time_left.data_ptr(), t.data_ptr(), _ptr(fired), n, dt, _ptr(interval_draws),
+                                    _ptr(push_draws), seed & 0xFFFFFFFFFFFFFFFF, env_offset, stream),
+          "as_events_interval")
 
 
 def unpack_report_ids(w):
@@ -258,6 +284,8 @@ def load() -> C.CDLL:
     L.as_contact_forces.argtypes = [V, V, V, V, V]
     L.as_noise_actions.argtypes = [V, V, V, I32, I32, V, V, U64, I64, V]
     L.as_noise_post.argtypes = [V, V, V, I32, I32, V, V, V, V, V, V, U64, I64, V]
+    L.as_events_init.argtypes = [V, I32, V, V, I32, V, U64, I64, V]
+    L.as_events_interval.argtypes = [V, I32, V, V, V, V, V, I32, C.c_float, V, V, U64, I64, V]
     L.as_last_error.restype = C.c_char_p
     L.as_build_id.restype = C.c_char_p
     for name in EXPORTED_SYMBOLS:

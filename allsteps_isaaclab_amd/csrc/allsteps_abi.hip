@@ -2,6 +2,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
 #include <cstdio>
 #include <cstring>
@@ -10,6 +11,7 @@
 
 #include "../../include/allsteps.h"
 #include "allsteps_kernels.h"
+#include "allsteps_events.h"
 #include "allsteps_noise.h"
 
 namespace {
@@ -614,6 +616,63 @@ int as_noise_post(const as_noise_model_t* action_model, const as_noise_model_t* 
   a.seed = seed;
   a.env_offset = env_id_offset;
   HIP_TRY(as::launch_noise_post(a, reinterpret_cast<hipStream_t>(stream)));
+  return AS_OK;
+}
+
+static bool events_shape_ok(int32_t num_terms, int32_t n, const std::string& what, std::string& err) {
+  if (num_terms < 1 || num_terms > AS_MAX_EVENT_TERMS)
+    err = what + ": num_terms " + std::to_string(num_terms) + " outside [1, AS_MAX_EVENT_TERMS = " +
+          std::to_string(AS_MAX_EVENT_TERMS) + "]";
+  else if (n < 1 || n > AS_MAX_ENVS)
+    err = what + ": n " + std::to_string(n) + " outside [1, AS_MAX_ENVS]";
+  else
+    return true;
+  return false;
+}
+
+int as_events_init(const as_event_term_t* terms, int32_t num_terms, float* time_left, uint32_t* t, int32_t n,
+                   const float* interval_draws, uint64_t seed, int64_t env_id_offset, void* stream) {
+  if (!terms || !time_left || !t) return fail(AS_ERR_INVALID, "as_events_init: null argument (terms / time_left / t)");
+  std::string err;
+  if (!events_shape_ok(num_terms, n, "as_events_init", err)) return fail(AS_ERR_INVALID, err);
+  as::EventsArgs a{};
+  a.terms = terms;
+  a.num_terms = num_terms;
+  a.n = n;
+  a.time_left = time_left;
+  a.t = t;
+  a.interval_draws = interval_draws;
+  a.seed = seed;
+  a.env_offset = env_id_offset;
+  HIP_TRY(as::launch_events_init(a, reinterpret_cast<hipStream_t>(stream)));
+  return AS_OK;
+}
+
+int as_events_interval(const as_event_term_t* terms, int32_t num_terms, float* root_lin, float* root_ang,
+                       float* time_left, uint32_t* t, uint8_t* fired, int32_t n, float dt,
+                       const float* interval_draws, const float* push_draws, uint64_t seed, int64_t env_id_offset,
+                       void* stream) {
+  if (!terms || !root_lin || !root_ang || !time_left || !t)
+    return fail(AS_ERR_INVALID, "as_events_interval: null argument (terms / root_lin / root_ang / time_left / t)");
+  std::string err;
+  if (!events_shape_ok(num_terms, n, "as_events_interval", err)) return fail(AS_ERR_INVALID, err);
+  if (!(dt > 0.f) || !std::isfinite(dt))
+    return fail(AS_ERR_INVALID, "as_events_interval: dt " + std::to_string(dt) + " is not a positive finite step");
+  as::EventsArgs a{};
+  a.terms = terms;
+  a.num_terms = num_terms;
+  a.n = n;
+  a.root_lin = root_lin;
+  a.root_ang = root_ang;
+  a.time_left = time_left;
+  a.t = t;
+  a.fired = fired;
+  a.interval_draws = interval_draws;
+  a.push_draws = push_draws;
+  a.dt = dt;
+  a.seed = seed;
+  a.env_offset = env_id_offset;
+  HIP_TRY(as::launch_events_interval(a, reinterpret_cast<hipStream_t>(stream)));
   return AS_OK;
 }
 

@@ -183,7 +183,27 @@ struct NoisePostArgs {
   int64_t env_offset;
 };
 
+// k_events_interval / k_events_init (as_events_interval / as_events_init, event_kernels.h): every buffer
+// field-major / env-minor.  k_events_init reads terms, num_terms, n, time_left, t, interval_draws, seed,
+// env_offset only
+struct EventsArgs {
+  const as_event_term_t* terms;  // [num_terms] device memory
+  int32_t num_terms, n;
+  float* root_lin;               // [3][n]
+  float* root_ang;               // [3][n]
+  float* time_left;              // [num_terms][n]
+  uint32_t* t;                   // [n] per-env counter of the event streams
+  uint8_t* fired;                // [num_terms][n] or null: not written
+  const float* interval_draws;   // [num_terms][n] injected draws or null: Philox
+  const float* push_draws;       // [num_terms][6][n] injected draws or null: Philox
+  float dt;
+  uint64_t seed;
+  int64_t env_offset;
+};
+
 bool step_supported_nv(int nv);
+hipError_t launch_events_interval(const EventsArgs& a, hipStream_t stream);
+hipError_t launch_events_init(const EventsArgs& a, hipStream_t stream);
 hipError_t launch_noise_actions(const NoiseActArgs& a, hipStream_t stream);
 hipError_t launch_noise_post(const NoisePostArgs& a, hipStream_t stream);
 hipError_t launch_contact_forces(const ForcesArgs& a, hipStream_t stream);

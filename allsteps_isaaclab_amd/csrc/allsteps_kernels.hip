@@ -458,6 +458,7 @@ __global__ __launch_bounds__(kStepThreads) __attribute__((amdgpu_waves_per_eu(2,
 #include "body_state_kernel.h"
 #include "contact_forces_kernel.h"
 #include "noise_kernels.h"
+#include "event_kernels.h"
 
 namespace as {
 
@@ -526,6 +527,19 @@ hipError_t launch_noise_post(const NoisePostArgs& a, hipStream_t stream) {
   const int64_t threads = (int64_t)a.n << a.gshift;
   hipLaunchKernelGGL(k_noise_post, dim3((unsigned)((threads + kNoiseThreads - 1) / kNoiseThreads)),
                      dim3(kNoiseThreads), 0, stream, a);
+  return hipGetLastError();
+}
+
+// one thread per env (n <= AS_MAX_ENVS = 2^24: at most 2^16 workgroups)
+hipError_t launch_events_interval(const EventsArgs& a, hipStream_t stream) {
+  hipLaunchKernelGGL(k_events_interval, dim3((unsigned)((a.n + kEventThreads - 1) / kEventThreads)),
+                     dim3(kEventThreads), 0, stream, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_events_init(const EventsArgs& a, hipStream_t stream) {
+  hipLaunchKernelGGL(k_events_init, dim3((unsigned)((a.n + kEventThreads - 1) / kEventThreads)),
+                     dim3(kEventThreads), 0, stream, a);
   return hipGetLastError();
 }
 

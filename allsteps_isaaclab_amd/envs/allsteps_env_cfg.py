@@ -80,6 +80,12 @@ class AllstepsEnvCfg:
     # one launch more per step for an observation model, two with an action model; None: the step as ever.
     action_noise_model: object = None
     observation_noise_model: object = None
+    # Events of DirectRLEnvCfg (direct_rl_env_cfg.py `events`): a dict or cfg object of utils.events EventTermCfg
+    # (the reference's isaaclab.managers class) or None.  Served: push_by_setting_velocity in "interval" mode --
+    # per-env timers, the push added to the root velocity -- in one HIP kernel after the step
+    # (csrc/event_kernels.h), one launch more per step; anything else raises at construction.  None: the step as
+    # ever.
+    events: object = None
 
     # joint gears, cfg/PhysX dof order (allsteps_env_cfg.py:133-155)
     joint_gears: list = field(default_factory=lambda: [

@@ -87,6 +87,8 @@ class AnymalCStonesEnvCfg:
     # noise models (as AllstepsEnvCfg's): a utils.noise NoiseModelCfg / NoiseModelWithAdditiveBiasCfg or None
     action_noise_model: object = None
     observation_noise_model: object = None
+    # interval events (as AllstepsEnvCfg's): a dict or cfg object of utils.events EventTermCfg or None
+    events: object = None
 
     # the stepping-stone task (authored; include/allsteps.h as_quad_task_t): the ALLSTEPS target
     # machine and reward terms (allsteps_env.py:347-394, 418-457) on four feet

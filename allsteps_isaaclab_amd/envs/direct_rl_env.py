@@ -44,6 +44,14 @@ class DirectRLEnv:
 
         self._noise = (EnvNoise(cfg, self.num_envs, self._device, cfg.seed if cfg.seed is not None else 0)
                        if EnvNoise.wanted(cfg) else None)
+        # cfg.events (direct_rl_env.py:148-149): device state of the interval-event kernel and env.event_manager,
+        # or None -- then step() launches nothing for it and nothing is allocated
+        from .events import EnvEvents, EventManagerView
+
+        self._events = (EnvEvents(cfg, self.num_envs, self._device, cfg.seed if cfg.seed is not None else 0,
+                                  self.step_dt) if EnvEvents.wanted(cfg) else None)
+        if self._events is not None:
+            self.event_manager = EventManagerView(self._events)
 
     # ------------------------------------------------------------------ properties
     @property
@@ -98,13 +106,18 @@ class DirectRLEnv:
     def step(self, action: torch.Tensor):
         """direct_rl_env.py:296-383: one env step (decimation physics substeps inside).  With noise models:
         the action model's output is what the step, ``env.actions`` and the action cost see (:322-323); the
-        envs the step reset get new biases (:578-581) and the policy observation is noised in place (:379-380)."""
+        envs the step reset get new biases (:578-581) and the policy observation is noised in place (:379-380).
+        With cfg.events: the interval terms run after the step and before the observation noise (:370-372); a
+        push is first seen by the next step's physics, as in the reference, where the observation, reward and
+        dones of the firing step are made from values cached before it."""
         action = action.to(self._device)
         self._sim_step_counter += self.cfg.decimation
         nz = self._noise
         if nz is not None and nz.action is not None:
             action = nz.apply_actions(action, self._noise_offset(), self._noise_stream())
         out = self._step_impl(action)
+        if self._events is not None:
+            self._events.apply(*self._events_root_velocity(), self._noise_offset(), self._noise_stream())
         if nz is not None:
             nz.post(out[0]["policy"], out[2], out[3], self._noise_offset(), self._noise_stream())
         self.common_step_counter += 1
@@ -134,6 +147,28 @@ class DirectRLEnv:
         if self._noise is not None:
             self._noise.set_state(state)
         return {k: v for k, v in state.items() if k not in EnvNoise.STATE_KEYS}
+
+    # ------------------------------------------------------------------ interval events
+    def _events_root_velocity(self):
+        """(root_lin, root_ang): the (3, num_envs) device rows the push terms write (subclass hook)."""
+        raise NotImplementedError(f"{type(self).__name__} does not expose a root velocity for cfg.events")
+
+    def _events_start(self) -> None:
+        """Draw the initial timers once the subclass knows its stream and env_id_offset."""
+        if self._events is not None:
+            self._events.start(self._noise_offset(), self._noise_stream())
+
+    def _events_get_state(self) -> dict:
+        """The event streams' counter and timers for get_state (no keys without cfg.events)."""
+        return {} if self._events is None else self._events.get_state()
+
+    def _events_set_state(self, state: dict) -> dict:
+        """Load the event keys of a set_state dict; returns the dict without them."""
+        from .events import EnvEvents
+
+        if self._events is not None:
+            self._events.set_state(state)
+        return {k: v for k, v in state.items() if k not in EnvEvents.STATE_KEYS}
 
     @staticmethod
     def seed(seed: int = -1) -> int:
@@ -172,9 +207,12 @@ class DirectRLEnv:
 
     # ------------------------------------------------------------------ subclass hooks
     def _reseed(self, seed: int):
-        """Re-seed the device streams (subclasses extend it): here the noise models' Philox key."""
+        """Re-seed the device streams (subclasses extend it): here the Philox key of the noise models and of
+        the interval events (whose timers stay as they are: DirectRLEnv never resets the event manager)."""
         if self._noise is not None:
             self._noise.seed = int(seed)
+        if self._events is not None:
+            self._events.seed = int(seed)
 
     def _reset_impl(self):
         raise NotImplementedError

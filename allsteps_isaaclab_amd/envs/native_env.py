@@ -34,6 +34,7 @@ class NativeDirectEnv(DirectRLEnv):
             self._launches = 0  # launches that change the report (the views' cache key beside the step counters)
             on = self.cfg.contact_forces if contact_forces is None else contact_forces
             self._report = _ContactReport(self, int(self.cfg.decimation)) if on else None
+            self._events_start()
 
     episode_length_buf = property(lambda self: self.state["ep_len"])
 
@@ -41,6 +42,9 @@ class NativeDirectEnv(DirectRLEnv):
         return torch.cuda.current_stream(self._device).cuda_stream
 
     _noise_stream = _stream
+
+    def _events_root_velocity(self):
+        return self.state["root_lin"], self.state["root_ang"]
 
     def _report_or_raise(self, what: str) -> _ContactReport:
         if self._report is None:
@@ -65,11 +69,13 @@ class NativeDirectEnv(DirectRLEnv):
 
     def get_state(self) -> dict:
         """Copy of the full SoA state (field -> (rows, N) tensor); with a noise model, also the noise
-        stream's counter and biases (noise_t, noise_action_bias, noise_obs_bias)."""
-        return {**{k: v.clone() for k, v in self.state.items()}, **self._noise_get_state()}
+        stream's counter and biases (noise_t, noise_action_bias, noise_obs_bias); with cfg.events, the event
+        streams' counter and timers (event_t, event_time_left)."""
+        return {**{k: v.clone() for k, v in self.state.items()}, **self._noise_get_state(),
+                **self._events_get_state()}
 
     def set_state(self, state: dict):
-        for k, v in self._noise_set_state(state).items():
+        for k, v in self._events_set_state(self._noise_set_state(state)).items():
             self.state[k].copy_(torch.as_tensor(v).to(self.state[k].device, self.state[k].dtype).reshape(
                 self.state[k].shape))
 

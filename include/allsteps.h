@@ -378,7 +378,39 @@ int as_noise_post(const as_noise_model_t* action_model, const as_noise_model_t* 
                   const float* action_bias_draws, const float* obs_bias_draws, uint64_t seed,
                   int64_t env_id_offset, void* stream);
 
-/* The H^-1 sweep plan for a model (round 6, ABI 5; no device needed).  The step kernel sweeps the
+/* Interval events, off by default: the "interval" terms of cfg.events that DirectRLEnv.step applies after
+ * _reset_idx and before _get_observations (direct_rl_env.py:370-372; EventManager.apply,
+ * isaaclab/managers/event_manager.py:200-225).  One term is served: push_by_setting_velocity
+ * (isaaclab/envs/mdp/events.py:681-706), which adds a uniform sample to the root velocity.  Stateless entry
+ * points over caller-owned device buffers, as the noise models' -- no as_env_t: the caller launches
+ * as_events_interval after as_step on the same stream (envs/direct_rl_env.py).  In the reference the push
+ * does not reach the observation, reward or dones of the step in which it fires (they are made from values
+ * cached before it); the next step's physics sees it first, which is what a launch after as_step gives.
+ * Every buffer is field-major / env-minor: root_lin [3][n] and root_ang [3][n] (as_state_t's), time_left
+ * [num_terms][n], t [n] (the per-env counter of the event streams), fired [num_terms][n].  Semantics, the
+ * float32 rounding order and the Philox stream layout (seed, env_id_offset + e, t[e], term block, tag):
+ * csrc/allsteps_events.h.  Both calls are graph-safe: nothing per call comes from the host but the pointers
+ * and the fixed dt; the term descriptors are read from device memory at every launch. */
+#define AS_MAX_EVENT_TERMS 4
+typedef struct {
+  float interval_lo, interval_w; /* interval_range_s: lo and float32(double(hi) - double(lo)) */
+  float vel_lo[6], vel_w[6];     /* velocity_range x y z roll pitch yaw: float32(lo), float32(hi) - float32(lo) */
+} as_event_term_t;
+/* The initial timers: time_left[k][e] = u w + lo from the interval stream's draw at counter 0 (or from
+ * interval_draws [num_terms][n], NULL: Philox), then t[e] = 1.  terms: num_terms descriptors in device memory. */
+int as_events_init(const as_event_term_t* terms, int32_t num_terms, float* time_left, uint32_t* t, int32_t n,
+                   const float* interval_draws, uint64_t seed, int64_t env_id_offset, void* stream);
+/* One env step of every term in one launch, terms in order: time_left -= dt; where time_left < 1e-6 the term
+ * fires: time_left is resampled and the push added to (root_lin, root_ang).  Then t[e] += 1.  fired: NULL or
+ * [num_terms][n] uint8, written 0 / 1 for every (term, env).  interval_draws [num_terms][n], push_draws
+ * [num_terms][6][n]: injected uniforms in [0, 1), read only where a term fires, or NULL (Philox streams at
+ * t[e]).  1 <= num_terms <= AS_MAX_EVENT_TERMS. */
+int as_events_interval(const as_event_term_t* terms, int32_t num_terms, float* root_lin, float* root_ang,
+                       float* time_left, uint32_t* t, uint8_t* fired, int32_t n, float dt,
+                       const float* interval_draws, const float* push_draws, uint64_t seed, int64_t env_id_offset,
+                       void* stream);
+
+/* The H^-1 sweep plan for a model (round 6, ABI 5; no device needed). The step kernel sweeps the
  * padded joint-space inertia last block first and, for the trees it is compiled for (the walker, the
  * C5 quadruped), skips the column quads in which the pivot rows are structurally zero -- an exact
  * identity, so results do not depend on it.  Returns 1 when the compiled skips hold for `model` (as_create
