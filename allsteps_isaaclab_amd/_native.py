@@ -27,12 +27,14 @@ EXPORTED_SYMBOLS = [
     "as_profile_sampled", "as_hbm_copy", "as_set_actuator", "as_set_quad_task", "as_quad_step", "as_quad_reset_all",
     "as_build_id", "as_step_counters_host", "as_body_state", "as_sweep_plan", "as_set_contact_report",
     "as_contact_forces", "as_noise_actions", "as_noise_post", "as_events_init", "as_events_interval",
+    "as_contact_timers",
 ]
 MAXB = 32  # AS_MAX_BODIES
 MAXC = 10  # AS_MAX_CONTACTS
 REPORT_WORDS = 8  # AS_REPORT_WORDS: lambda_n n (3) | contact point (3) | separation | packed ids
 REPORT_FEET = 4  # AS_REPORT_FEET
 NUM_STONES = 20  # AS_NUM_STONES
+TIMER_ROWS = 4  # as_contact_timers rows: current_air, last_air, current_contact, last_contact
 BODY_STATE_ROWS = 16  # AS_BODY_STATE_ROWS: pos 3 | quat 4 | frame lin vel 3 | ang vel 3 | COM lin vel 3
 
 
@@ -282,6 +284,7 @@ def load() -> C.CDLL:
     L.as_sweep_plan.argtypes = [V, C.POINTER(C.c_uint64)]
     L.as_set_contact_report.argtypes = [V, V]
     L.as_contact_forces.argtypes = [V, V, V, V, V]
+    L.as_contact_timers.argtypes = [V, V, V, V, C.c_float, I32, V, V, V]
     L.as_noise_actions.argtypes = [V, V, V, I32, I32, V, V, U64, I64, V]
     L.as_noise_post.argtypes = [V, V, V, I32, I32, V, V, V, V, V, V, U64, I64, V]
     L.as_events_init.argtypes = [V, I32, V, V, I32, V, U64, I64, V]
@@ -505,6 +508,15 @@ class NativeEnv:
         [depth][num_bodies][3][n] (impulses, N s) from the report as it stands."""
         check(self.L.as_contact_forces(self.h, C.byref(table) if table is not None else None,
                                        _ptr(force_matrix_out), _ptr(net_out), stream), "as_contact_forces")
+
+    def contact_timers(self, table: "AsBodyTable", timers, timestamp, force_threshold: float, updates: int,
+                       reset=None, reset2=None, stream=None):
+        """as_contact_timers: `updates` (0 or the report's depth) sensor updates of timers fp32 [TIMER_ROWS]
+        [num_bodies][n] and timestamp fp32 [n] from the report as it stands, then the reset of the envs in reset |
+        reset2 ([n] uint8 / bool; reset None: all when updates == 0, none otherwise)."""
+        check(self.L.as_contact_timers(self.h, C.byref(table) if table is not None else None, _ptr(timers),
+                                       _ptr(timestamp), force_threshold, int(updates), _ptr(reset), _ptr(reset2),
+                                       stream), "as_contact_timers")
 
     def set_actuator(self, mode: int, action_scale: float = 0.0, default_q=(), stiffness: float = 0.0,
                      damping: float = 0.0, saturation_effort: float = 0.0, effort_limit: float = 0.0,

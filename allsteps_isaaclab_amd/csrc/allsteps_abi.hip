@@ -530,6 +530,43 @@ int as_contact_forces(as_env_t* env, const as_body_table_t* bodies_host, float* 
   return AS_OK;
 }
 
+int as_contact_timers(as_env_t* env, const as_body_table_t* bodies_host, float* timers, float* timestamp,
+                      float force_threshold, int32_t updates, const uint8_t* reset, const uint8_t* reset2,
+                      void* stream) {
+  if (!env || !bodies_host || !timers || !timestamp)
+    return fail(AS_ERR_INVALID, "as_contact_timers: null argument (env / bodies / timers / timestamp)");
+  if (!env->report.count) return fail(AS_ERR_INVALID, "as_contact_timers: no contact report set (as_set_contact_report)");
+  if (updates != 0 && updates != env->report.depth)
+    return fail(AS_ERR_INVALID, "as_contact_timers: updates " + std::to_string(updates) + " is neither 0 nor the " +
+                                    "report's depth " + std::to_string(env->report.depth));
+  if (!reset && reset2) return fail(AS_ERR_INVALID, "as_contact_timers: reset2 without reset");
+  if (!(force_threshold >= 0.f) || !std::isfinite(force_threshold))
+    return fail(AS_ERR_INVALID, "as_contact_timers: force_threshold " + std::to_string(force_threshold) +
+                                    " is not a finite non-negative force");
+  const as_body_table_t& b = *bodies_host;
+  if (b.num_bodies < 1 || b.num_bodies > AS_MAX_BODIES)
+    return fail(AS_ERR_INVALID, "as_contact_timers: num_bodies out of range [1, AS_MAX_BODIES]");
+  as::TimersArgs a{};
+  for (int i = 0; i < b.num_bodies; ++i) {
+    if (b.link[i] < 0 || b.link[i] >= env->host.model.num_links)
+      return fail(AS_ERR_INVALID, "as_contact_timers: body link out of range");
+    a.link[i] = b.link[i];
+  }
+  a.n = env->n;
+  a.updates = updates;
+  a.count = env->report.count;
+  a.records = env->report.records;
+  a.timers = timers;
+  a.timestamp = timestamp;
+  a.reset = reset;
+  a.reset2 = reset2;
+  a.dt = env->host.sim.dt;
+  a.force_threshold = force_threshold;
+  a.num_bodies = b.num_bodies;
+  HIP_TRY(as::launch_contact_timers(a, reinterpret_cast<hipStream_t>(stream)));
+  return AS_OK;
+}
+
 // as_noise_*: a model's ranges and pointers.  `what` names the call and the model in the message.
 static bool noise_model_ok(const as_noise_model_t& m, const std::string& what, std::string& err) {
   if (m.kind < AS_NOISE_CONSTANT || m.kind > AS_NOISE_GAUSSIAN)

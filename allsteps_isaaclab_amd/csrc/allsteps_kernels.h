@@ -201,7 +201,25 @@ struct EventsArgs {
   int64_t env_offset;
 };
 
+// k_contact_timers (as_contact_timers, contact_timer_kernels.h): the air / contact timers over the contact
+// report; every buffer field-major / env-minor
+struct TimersArgs {
+  int32_t n;
+  int32_t updates;             // sensor updates to apply: 0 (reset only) or the report's depth
+  const int32_t* count;
+  const uint32_t* records;
+  float* timers;               // [kTimerRows][nb][n]
+  float* timestamp;            // [n]
+  const uint8_t* reset;        // [n] envs reset after the updates, or null: all when updates == 0, else none
+  const uint8_t* reset2;       // [n] a second mask, ORed with the first, or null
+  float dt;                    // sim.dt
+  float force_threshold;
+  int32_t num_bodies;
+  int32_t link[AS_MAX_BODIES];
+};
+
 bool step_supported_nv(int nv);
+hipError_t launch_contact_timers(const TimersArgs& a, hipStream_t stream);
 hipError_t launch_events_interval(const EventsArgs& a, hipStream_t stream);
 hipError_t launch_events_init(const EventsArgs& a, hipStream_t stream);
 hipError_t launch_noise_actions(const NoiseActArgs& a, hipStream_t stream);

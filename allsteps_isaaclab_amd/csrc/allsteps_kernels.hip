@@ -25,7 +25,8 @@
 //   H^-1 sweep -> step_collide.h  contacts -> step_solve.h  rows, PGS, substep -> step_report.h  the opt-in
 //   contact report's stores -> step_task.h  task helpers;
 // after k_step: task_kernels.h (k_obs, k_stones, k_quad), body_state_kernel.h (k_body_state) and
-// contact_forces_kernel.h (k_contact_forces).
+// contact_forces_kernel.h (k_contact_forces), noise_kernels.h, event_kernels.h and contact_timer_kernels.h
+// (k_contact_timers).
 #include <hip/hip_runtime.h>
 
 #include "../../include/allsteps.h"
@@ -459,6 +460,7 @@ __global__ __launch_bounds__(kStepThreads) __attribute__((amdgpu_waves_per_eu(2,
 #include "contact_forces_kernel.h"
 #include "noise_kernels.h"
 #include "event_kernels.h"
+#include "contact_timer_kernels.h"
 
 namespace as {
 
@@ -540,6 +542,13 @@ hipError_t launch_events_interval(const EventsArgs& a, hipStream_t stream) {
 hipError_t launch_events_init(const EventsArgs& a, hipStream_t stream) {
   hipLaunchKernelGGL(k_events_init, dim3((unsigned)((a.n + kEventThreads - 1) / kEventThreads)),
                      dim3(kEventThreads), 0, stream, a);
+  return hipGetLastError();
+}
+
+// kTimerEnvs envs x kTimerGroup body waves per workgroup (n <= AS_MAX_ENVS = 2^24: at most 2^18 workgroups)
+hipError_t launch_contact_timers(const TimersArgs& a, hipStream_t stream) {
+  hipLaunchKernelGGL(k_contact_timers, dim3((unsigned)((a.n + kTimerEnvs - 1) / kTimerEnvs)),
+                     dim3(kTimerEnvs, kTimerGroup), 0, stream, a);
   return hipGetLastError();
 }
 

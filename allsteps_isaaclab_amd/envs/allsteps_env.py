@@ -123,6 +123,7 @@ class AllstepsEnv(NativeDirectEnv):
         observation buffer.  ``env_ids``: indices, a bool mask, or None (all envs)."""
         if env_ids is None:
             obs = self._reset_impl(reset_draws)
+            self._sensors_reset(None)
             self._noise_reset(None)
             return obs
         ids = torch.as_tensor(env_ids, device=self._device)
@@ -139,6 +140,7 @@ class AllstepsEnv(NativeDirectEnv):
         obs = torch.empty(self.num_envs, self.cfg.observation_space, device=self._device)
         d = None if reset_draws is None else reset_draws.to(self._device).float().contiguous()
         self._native.reset_mask(mask, obs, d, stream=self._stream())
+        self._sensors_reset(mask)
         self._noise_reset(mask)
         self.obs_buf = {"policy": obs}
         return self.obs_buf

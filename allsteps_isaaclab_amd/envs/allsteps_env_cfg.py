@@ -73,6 +73,14 @@ class AllstepsEnvCfg:
     # net_forces_w_history (contact_sensor.py:329-343, history_length = 4: allsteps_env_cfg.py:119-130) and
     # robot.data.joint_acc (articulation_data.py:547-556).  False: the step and its outputs as ever.
     contact_forces: bool = False
+    # The contact sensors' air / contact timers (ContactSensorCfg.track_air_time and force_threshold,
+    # contact_sensor_cfg.py:23-30): with True sensor*.data.current_air_time / last_air_time / current_contact_time /
+    # last_contact_time and sensor*.compute_first_contact / compute_first_air, advanced on the device by one HIP
+    # kernel after the step (csrc/contact_timer_kernels.h: `decimation` sensor updates per step, one launch more);
+    # a foot is in contact where the norm of its net contact force exceeds contact_force_threshold (N).  It
+    # builds the contact report itself, so the contact_forces views work too.  False: the step as ever.
+    contact_air_time: bool = False
+    contact_force_threshold: float = 1.0
     # Noise models of DirectRLEnvCfg (direct_rl_env_cfg.py:171, 208): a utils.noise NoiseModelCfg /
     # NoiseModelWithAdditiveBiasCfg (the reference's isaaclab.utils.noise classes) or None.  The action model
     # perturbs the action before the step, the observation model the policy observation after it, a bias model's

@@ -84,6 +84,9 @@ class AnymalCStonesEnvCfg:
     step_size: tuple = (0.5, 0.8, 0.225)
     # the opt-in contact report (as AllstepsEnvCfg.contact_forces): real foot forces and joint_acc views
     contact_forces: bool = False
+    # the four feet's air / contact timers (as AllstepsEnvCfg.contact_air_time / contact_force_threshold)
+    contact_air_time: bool = False
+    contact_force_threshold: float = 1.0
     # noise models (as AllstepsEnvCfg's): a utils.noise NoiseModelCfg / NoiseModelWithAdditiveBiasCfg or None
     action_noise_model: object = None
     observation_noise_model: object = None

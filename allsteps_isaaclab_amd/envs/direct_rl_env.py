@@ -24,6 +24,10 @@ class DirectRLEnv:
     is_vector_env = True
     metadata: dict = {"render_modes": [None, "rgb_array"], "isaac_sim_version": None}
     env_id_offset = 0  # a shard's first global env id (it enters the noise models' Philox key)
+    # Sensors that carry state from step to step (the contact sensors' air / contact timers), set by the subclass
+    # that owns them: an object with update(terminated, truncated) -- the step's sensor updates, then the reset of
+    # the envs the step reset -- and reset(mask).  None: step() launches nothing for it.
+    _sensors = None
 
     def __init__(self, cfg, render_mode: str | None = None, **kwargs):
         self.cfg = cfg
@@ -100,6 +104,7 @@ class DirectRLEnv:
             self.seed(seed)
             self._reseed(seed)
         obs = self._reset_impl()
+        self._sensors_reset(None)
         self._noise_reset(None)  # the returned observation is not noised (direct_rl_env.py:294)
         return obs, self.extras
 
@@ -109,13 +114,18 @@ class DirectRLEnv:
         envs the step reset get new biases (:578-581) and the policy observation is noised in place (:379-380).
         With cfg.events: the interval terms run after the step and before the observation noise (:370-372); a
         push is first seen by the next step's physics, as in the reference, where the observation, reward and
-        dones of the firing step are made from values cached before it."""
+        dones of the firing step are made from values cached before it.  With stateful sensors (the contact
+        sensors' air / contact timers): their update for the step's substeps and the reset of the envs the step
+        reset (:347, :361) follow the step directly.  Only ``step`` drives them -- a subclass's bare physics or
+        task launches do not."""
         action = action.to(self._device)
         self._sim_step_counter += self.cfg.decimation
         nz = self._noise
         if nz is not None and nz.action is not None:
             action = nz.apply_actions(action, self._noise_offset(), self._noise_stream())
         out = self._step_impl(action)
+        if self._sensors is not None:  # before the events, as a fixed order: the two touch disjoint buffers
+            self._sensors.update(out[2], out[3])
         if self._events is not None:
             self._events.apply(*self._events_root_velocity(), self._noise_offset(), self._noise_stream())
         if nz is not None:
@@ -147,6 +157,13 @@ class DirectRLEnv:
         if self._noise is not None:
             self._noise.set_state(state)
         return {k: v for k, v in state.items() if k not in EnvNoise.STATE_KEYS}
+
+    # ------------------------------------------------------------------ stateful sensors
+    def _sensors_reset(self, mask: torch.Tensor | None) -> None:
+        """Sensor.reset(env_ids) for the envs of a uint8 mask (None: all) -- reset() calls it, and the subclass's
+        other reset paths after their own reset."""
+        if self._sensors is not None:
+            self._sensors.reset(mask)
 
     # ------------------------------------------------------------------ interval events
     def _events_root_velocity(self):

@@ -9,17 +9,20 @@ import torch
 from .. import _native
 from .direct_rl_env import DirectRLEnv
 from .state import alloc_state
-from .views import _ContactReport
+from .views import _ContactReport, _ContactTimers
 
 
 class NativeDirectEnv(DirectRLEnv):
     _native = None  # the NativeEnv handle: None before _init_native and after close
+    _contact_timers = None  # the _ContactTimers of cfg.contact_air_time, or None: nothing allocated or launched
 
     def _init_native(self, model: dict, *, hind: bool = False, feet: bool = False, env_id_offset: int = 0,
                      contact_forces: bool | None = None) -> None:
         """After ``DirectRLEnv.__init__``: the zeroed device state (``alloc_state(n, device, hind=, feet=)``), the
         handle over it, seeded with ``cfg.seed``, and the contact report when ``cfg.contact_forces`` (or the
-        constructor's override ``contact_forces``) asks for one.  Env-specific initial values are the caller's."""
+        constructor's override ``contact_forces``) or ``cfg.contact_air_time`` asks for one -- the timers read the
+        report, so they bring it (and with it the force views) whether or not the forces were asked for.
+        Env-specific initial values are the caller's."""
         dev = self._device
         if dev.type != "cuda" or not torch.cuda.is_available():
             raise _native.NativeError(f"{type(self).__name__} runs on the HIP backend only (device={dev}, HIP device "
@@ -33,7 +36,11 @@ class NativeDirectEnv(DirectRLEnv):
                                              self.env_id_offset)
             self._launches = 0  # launches that change the report (the views' cache key beside the step counters)
             on = self.cfg.contact_forces if contact_forces is None else contact_forces
-            self._report = _ContactReport(self, int(self.cfg.decimation)) if on else None
+            air = bool(getattr(self.cfg, "contact_air_time", False))
+            self._report = _ContactReport(self, int(self.cfg.decimation)) if on or air else None
+            self._contact_timers = (_ContactTimers(self, self._report, self.cfg.contact_force_threshold)
+                                    if air else None)
+            self._sensors = self._contact_timers  # DirectRLEnv.step / reset drive them
             self._events_start()
 
     episode_length_buf = property(lambda self: self.state["ep_len"])
@@ -70,11 +77,16 @@ class NativeDirectEnv(DirectRLEnv):
     def get_state(self) -> dict:
         """Copy of the full SoA state (field -> (rows, N) tensor); with a noise model, also the noise
         stream's counter and biases (noise_t, noise_action_bias, noise_obs_bias); with cfg.events, the event
-        streams' counter and timers (event_t, event_time_left)."""
+        streams' counter and timers (event_t, event_time_left); with cfg.contact_air_time, the sensors' timers and
+        timestamp (contact_timers (4, B, N), contact_timestamp (N,))."""
+        tm = self._contact_timers
         return {**{k: v.clone() for k, v in self.state.items()}, **self._noise_get_state(),
-                **self._events_get_state()}
+                **self._events_get_state(), **({} if tm is None else tm.get_state())}
 
     def set_state(self, state: dict):
+        if self._contact_timers is not None:
+            self._contact_timers.set_state(state)
+        state = {k: v for k, v in state.items() if k not in _ContactTimers.STATE_KEYS}
         for k, v in self._events_set_state(self._noise_set_state(state)).items():
             self.state[k].copy_(torch.as_tensor(v).to(self.state[k].device, self.state[k].dtype).reshape(
                 self.state[k].shape))

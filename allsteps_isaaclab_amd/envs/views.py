@@ -153,6 +153,29 @@ class _SensorData:
         reference's history_length = 4 at one sensor update per physics step)."""
         return self._sensor._net_forces()
 
+    # ``cfg.contact_air_time`` (the reference's track_air_time, contact_sensor_data.py:68-101): (N, B) zero-copy
+    # views of the env's one set of timers, which k_contact_timers advances by `decimation` sensor updates in
+    # every ``env.step``; None when the feature is off, as in the reference
+    @property
+    def current_air_time(self) -> torch.Tensor | None:
+        """(N, B) time (s) spent in the air since the last detach."""
+        return self._sensor._timer(0)
+
+    @property
+    def last_air_time(self) -> torch.Tensor | None:
+        """(N, B) time (s) spent in the air before the last contact."""
+        return self._sensor._timer(1)
+
+    @property
+    def current_contact_time(self) -> torch.Tensor | None:
+        """(N, B) time (s) spent in contact since the last contact."""
+        return self._sensor._timer(2)
+
+    @property
+    def last_contact_time(self) -> torch.Tensor | None:
+        """(N, B) time (s) spent in contact before the last detach."""
+        return self._sensor._timer(3)
+
 
 class _FootSensor:
     """The reference's foot ContactSensors (allsteps_env_cfg.py:119-130; contact_sensor.py:320-343):
@@ -186,6 +209,33 @@ class _FootSensor:
         _, net = rep.forces()  # (T, bodies, 3, N) impulses
         return net[:, [rep.foot_body[f] for f in self._feet]].permute(3, 0, 1, 2) / self._env.cfg.sim.dt
 
+    def _timer(self, row: int) -> torch.Tensor | None:
+        """(N, B) view of timer `row` of this sensor's bodies (its feet are consecutive in sensor order)."""
+        tm = self._env._contact_timers
+        return None if tm is None else tm.timers[row, self._feet[0]: self._feet[-1] + 1].T
+
+    def _timers_or_raise(self) -> None:
+        # the reference's message (contact_sensor.py:201-205, 236-240); its track_air_time is cfg.contact_air_time
+        if self._env._contact_timers is None:
+            raise RuntimeError("The contact sensor is not configured to track contact time."
+                               "Please enable the 'track_air_time' in the sensor configuration.")
+
+    def compute_first_contact(self, dt: float, abs_tol: float = 1.0e-8) -> torch.Tensor:
+        """(N, B) bool: the bodies that established contact within the last ``dt`` seconds
+        (contact_sensor.py:175-209).  ``cfg.contact_air_time`` only."""
+        self._timers_or_raise()
+        currently_in_contact = self.data.current_contact_time > 0.0
+        less_than_dt_in_contact = self.data.current_contact_time < (dt + abs_tol)
+        return currently_in_contact * less_than_dt_in_contact
+
+    def compute_first_air(self, dt: float, abs_tol: float = 1.0e-8) -> torch.Tensor:
+        """(N, B) bool: the bodies that broke contact within the last ``dt`` seconds (contact_sensor.py:211-244).
+        ``cfg.contact_air_time`` only."""
+        self._timers_or_raise()
+        currently_detached = self.data.current_air_time > 0.0
+        less_than_dt_detached = self.data.current_air_time < (dt + abs_tol)
+        return currently_detached * less_than_dt_detached
+
 
 class _ContactReport:
     """The opt-in contact report of an env (``cfg.contact_forces``; include/allsteps.h ABI 6): the device buffers
@@ -218,6 +268,55 @@ class _ContactReport:
             env._native.contact_forces(self._table, self._matrix, self._net, stream=env._stream())
             self._stamp = stamp
         return self._matrix, self._net
+
+
+class _ContactTimers:
+    """The air / contact timers of an env (``cfg.contact_air_time``; the reference's ContactSensor with
+    track_air_time = True, contact_sensor.py:351-379): device state of ``as_contact_timers`` over the env's contact
+    report.  One set serves every sensor of the env: body k is sensor foot k (walker: right, left; quadruped: RF,
+    LF, RH, LH).  ``update`` runs after every ``env.step`` (``decimation`` sensor updates, then the reset of the
+    envs the step reset), ``reset`` in the env's reset paths; both are one launch on the env's stream."""
+
+    STATE_KEYS = ("contact_timers", "contact_timestamp")
+
+    def __init__(self, env, report: _ContactReport, force_threshold: float):
+        n, dev = env.num_envs, env._device
+        self._env, self._depth = env, report.depth
+        self.force_threshold = float(force_threshold)
+        feet = sorted(report.foot_body)
+        if feet != list(range(len(feet))):
+            raise _native.NativeError(f"contact_air_time: the model's sensor feet {feet} are not 0 .. {len(feet) - 1}")
+        body_link = [int(x) for x in env.model["body_link"]]
+        self._table = _native.AsBodyTable()
+        self._table.num_bodies = len(feet)
+        for f in feet:
+            self._table.link[f] = body_link[report.foot_body[f]]
+        self.num_bodies = len(feet)
+        self.timers = torch.zeros(_native.TIMER_ROWS, len(feet), n, dtype=torch.float32, device=dev)
+        self.timestamp = torch.zeros(n, dtype=torch.float32, device=dev)
+
+    def update(self, terminated: torch.Tensor, truncated: torch.Tensor) -> None:
+        env = self._env
+        env._native.contact_timers(self._table, self.timers, self.timestamp, self.force_threshold, self._depth,
+                                   terminated, truncated, stream=env._stream())
+
+    def reset(self, mask: torch.Tensor | None) -> None:
+        """ContactSensor.reset(env_ids) for the envs of a uint8 / bool mask (None: all)."""
+        env = self._env
+        env._native.contact_timers(self._table, self.timers, self.timestamp, self.force_threshold, 0, mask, None,
+                                   stream=env._stream())
+
+    # ---- state (get_state / set_state of the envs)
+    def tensors(self) -> dict:
+        return {"contact_timers": self.timers, "contact_timestamp": self.timestamp}
+
+    def get_state(self) -> dict:
+        return {k: v.clone() for k, v in self.tensors().items()}
+
+    def set_state(self, state: dict) -> None:
+        for k, v in self.tensors().items():
+            if k in state:
+                v.copy_(torch.as_tensor(state[k]).to(v.device, v.dtype).reshape(v.shape))
 
 
 class _RobotView:

@@ -341,6 +341,27 @@ int as_set_contact_report(as_env_t* env, const as_contact_report_t* report);
  * Divide by sim.dt for forces.  AS_ERR_INVALID when no report is set or an argument is NULL. */
 int as_contact_forces(as_env_t* env, const as_body_table_t* bodies_host, float* force_matrix_out, float* net_out,
                       void* stream);
+/* The air / contact timers of the reference's ContactSensor with track_air_time = True (contact_sensor.py:351-379,
+ * 156-161; compute_first_contact / compute_first_air read them), off by default: one launch of k_contact_timers
+ * on `stream` over the report as it stands, never part of as_step -- the caller launches it after as_step
+ * (envs/direct_rl_env.py), so only steps made that way drive the timers, not bare as_physics_step calls.  One
+ * added symbol, no struct change: AS_ABI_VERSION stays 6.
+ *   timers    [4][num_bodies][n]  rows current_air, last_air, current_contact, last_contact (s), caller-owned,
+ *                                 zeroed at construction and kept with the state
+ *   timestamp [n]                 the sensor's float32 time since the env's last reset
+ * updates = the report's depth: every env applies `depth` sensor updates, oldest substep (slot depth - 1) first:
+ * timestamp += sim.dt; elapsed = the float32 difference of the two timestamps; a body is in contact where the
+ * norm of its net impulse (as_contact_forces' net_out: report_body_sum over its link, self-contacts with their
+ * sign) / sim.dt exceeds force_threshold; then the reference's four lines in its order
+ * (csrc/allsteps_contact_timers.h has the formulas and the float32 rounding order).  updates = 0: no update.
+ * Afterwards the envs with reset[e] | reset2[e] != 0 ([n] uint8 each; reset2 may be NULL) get zero timers and a
+ * zero timestamp; reset NULL: every env when updates = 0 (reset() and _reset_idx(None)), none otherwise.
+ * AS_ERR_INVALID when no report is set, updates is neither 0 nor the report's depth, reset2 comes without reset
+ * or timers / timestamp / bodies_host is NULL.  Graph-safe: nothing per call comes from the host but the pointers
+ * and the two scalars. */
+int as_contact_timers(as_env_t* env, const as_body_table_t* bodies_host, float* timers, float* timestamp,
+                      float force_threshold, int32_t updates, const uint8_t* reset, const uint8_t* reset2,
+                      void* stream);
 
 /* Noise models, off by default: DirectRLEnv.step's cfg.action_noise_model / cfg.observation_noise_model
  * (direct_rl_env.py:322-323, 379-380, 578-581; isaaclab/utils/noise/noise_model.py).  Stateless entry points
