@@ -27,7 +27,7 @@ EXPORTED_SYMBOLS = [
     "as_profile_sampled", "as_hbm_copy", "as_set_actuator", "as_set_quad_task", "as_quad_step", "as_quad_reset_all",
     "as_build_id", "as_step_counters_host", "as_body_state", "as_sweep_plan", "as_set_contact_report",
     "as_contact_forces", "as_noise_actions", "as_noise_post", "as_events_init", "as_events_interval",
-    "as_contact_timers",
+    "as_contact_timers", "as_ray_cast",
 ]
 MAXB = 32  # AS_MAX_BODIES
 MAXC = 10  # AS_MAX_CONTACTS
@@ -35,6 +35,9 @@ REPORT_WORDS = 8  # AS_REPORT_WORDS: lambda_n n (3) | contact point (3) | separa
 REPORT_FEET = 4  # AS_REPORT_FEET
 NUM_STONES = 20  # AS_NUM_STONES
 TIMER_ROWS = 4  # as_contact_timers rows: current_air, last_air, current_contact, last_contact
+MAX_RAYS = 1024  # AS_MAX_RAYS
+RAY_GROUND, RAY_STONES = 1, 2  # AS_RAY_GROUND, AS_RAY_STONES (as_ray_caster_t.surfaces)
+RAY_HIT_GROUND, RAY_MISS = -1, -2  # AS_RAY_HIT_GROUND, AS_RAY_MISS (as_ray_cast's surface)
 BODY_STATE_ROWS = 16  # AS_BODY_STATE_ROWS: pos 3 | quat 4 | frame lin vel 3 | ang vel 3 | COM lin vel 3
 
 
@@ -46,6 +49,12 @@ class AsBodyTable(C.Structure):
     """as_body_table_t (include/allsteps.h): the model's bodies for as_body_state."""
     _fields_ = [("num_bodies", C.c_int32), ("link", C.c_int32 * MAXB), ("offset_pos", (C.c_float * 3) * MAXB),
                 ("offset_quat", (C.c_float * 4) * MAXB), ("com", (C.c_float * 3) * MAXB)]
+
+
+class AsRayCaster(C.Structure):
+    """as_ray_caster_t (include/allsteps.h): what one as_ray_cast call casts against and how far."""
+    _fields_ = [("num_rays", C.c_int32), ("attach_yaw_only", C.c_int32), ("surfaces", C.c_int32),
+                ("max_distance", C.c_float), ("ground_z", C.c_float)]
 
 
 class AsContactReport(C.Structure):
@@ -285,6 +294,7 @@ def load() -> C.CDLL:
     L.as_set_contact_report.argtypes = [V, V]
     L.as_contact_forces.argtypes = [V, V, V, V, V]
     L.as_contact_timers.argtypes = [V, V, V, V, C.c_float, I32, V, V, V]
+    L.as_ray_cast.argtypes = [V, V, V, V, V, V, V]
     L.as_noise_actions.argtypes = [V, V, V, I32, I32, V, V, U64, I64, V]
     L.as_noise_post.argtypes = [V, V, V, I32, I32, V, V, V, V, V, V, U64, I64, V]
     L.as_events_init.argtypes = [V, I32, V, V, I32, V, U64, I64, V]
@@ -517,6 +527,13 @@ class NativeEnv:
         check(self.L.as_contact_timers(self.h, C.byref(table) if table is not None else None, _ptr(timers),
                                        _ptr(timestamp), force_threshold, int(updates), _ptr(reset), _ptr(reset2),
                                        stream), "as_contact_timers")
+
+    def ray_cast(self, cfg: "AsRayCaster", rays, hits, surface=None, pose=None, stream=None):
+        """as_ray_cast: the rays fp32 [6][num_rays] (device) from every env's root frame against the ground and the
+        stones of the state as it stands; hits fp32 [3][num_rays][n], surface int8 [num_rays][n] or None, pose
+        fp32 [7][n] or None."""
+        check(self.L.as_ray_cast(self.h, C.byref(cfg) if cfg is not None else None, _ptr(rays), _ptr(hits),
+                                 _ptr(surface), _ptr(pose), stream), "as_ray_cast")
 
     def set_actuator(self, mode: int, action_scale: float = 0.0, default_q=(), stiffness: float = 0.0,
                      damping: float = 0.0, saturation_effort: float = 0.0, effort_limit: float = 0.0,

@@ -13,6 +13,7 @@
 #include "allsteps_kernels.h"
 #include "allsteps_events.h"
 #include "allsteps_noise.h"
+#include "allsteps_ray_caster.h"
 
 namespace {
 
@@ -564,6 +565,44 @@ int as_contact_timers(as_env_t* env, const as_body_table_t* bodies_host, float* 
   a.force_threshold = force_threshold;
   a.num_bodies = b.num_bodies;
   HIP_TRY(as::launch_contact_timers(a, reinterpret_cast<hipStream_t>(stream)));
+  return AS_OK;
+}
+
+int as_ray_cast(as_env_t* env, const as_ray_caster_t* cfg_host, const float* rays, float* hits, int8_t* surface,
+                float* pose, void* stream) {
+  if (!env) return fail(AS_ERR_INVALID, "as_ray_cast: null argument env");
+  if (!cfg_host) return fail(AS_ERR_INVALID, "as_ray_cast: null argument cfg");
+  if (!rays) return fail(AS_ERR_INVALID, "as_ray_cast: null argument rays");
+  if (!hits) return fail(AS_ERR_INVALID, "as_ray_cast: null argument hits");
+  const as_ray_caster_t& c = *cfg_host;
+  if (c.num_rays < 1 || c.num_rays > AS_MAX_RAYS)
+    return fail(AS_ERR_INVALID, "as_ray_cast: num_rays " + std::to_string(c.num_rays) + " outside [1, AS_MAX_RAYS = " +
+                                    std::to_string(AS_MAX_RAYS) + "]");
+  if (c.surfaces == 0 || (c.surfaces & ~as::kRaySurfAll))
+    return fail(AS_ERR_INVALID, "as_ray_cast: surfaces " + std::to_string(c.surfaces) +
+                                    " is not AS_RAY_GROUND, AS_RAY_STONES or both");
+  if (!std::isfinite(c.max_distance) || !(c.max_distance > 0.f))
+    return fail(AS_ERR_INVALID, "as_ray_cast: max_distance " + std::to_string(c.max_distance) +
+                                    " is not a finite positive distance");
+  if (!std::isfinite(c.ground_z))
+    return fail(AS_ERR_INVALID, "as_ray_cast: ground_z " + std::to_string(c.ground_z) + " is not finite");
+  as::RayArgs a{};
+  a.n = env->n;
+  a.num_rays = c.num_rays;
+  a.attach_yaw_only = c.attach_yaw_only != 0;
+  a.surfaces = c.surfaces;
+  a.num_steps = env->host.task.num_steps;
+  a.max_distance = c.max_distance;
+  a.ground_z = c.ground_z;
+  for (int k = 0; k < 3; ++k) a.half[k] = env->host.sim.stone_half[k];
+  a.root_pos = env->st.root_pos;
+  a.root_quat = env->st.root_quat;
+  a.stones = env->st.stones;
+  a.rays = rays;
+  a.hits = hits;
+  a.surface = surface;
+  a.pose = pose;
+  HIP_TRY(as::launch_ray_cast(a, reinterpret_cast<hipStream_t>(stream)));
   return AS_OK;
 }
 

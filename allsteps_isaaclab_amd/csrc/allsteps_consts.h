@@ -14,6 +14,8 @@
 #include "../../include/as_detmath.h"  // AS_SWEEP_PAD (under hipcc its AS_HD wants hip_runtime.h first: allsteps_kernels.h)
 #include "allsteps_lane_table.h"
 
+#define AS_MAX_RAYS 1024  // rays of one as_ray_cast call (a ray-caster sensor's pattern)
+
 namespace as {
 
 constexpr int kMaxLinks = 24;  // LDS sizing of the step kernel (walker: 22 links)

@@ -218,7 +218,28 @@ struct TimersArgs {
   int32_t link[AS_MAX_BODIES];
 };
 
+// k_ray_cast (as_ray_cast, ray_caster_kernels.h): the height scanner's rays against the ground and the stones;
+// every buffer field-major / env-minor (allsteps_ray_caster.h)
+struct RayArgs {
+  int32_t n;
+  int32_t num_rays;
+  int32_t chunk;               // rays per slice (launch_ray_cast sizes it)
+  int32_t attach_yaw_only;
+  int32_t surfaces;            // AS_RAY_GROUND | AS_RAY_STONES
+  int32_t num_steps;           // stones per env
+  float max_distance, ground_z;
+  float half[3];               // sim.stone_half
+  const float* root_pos;       // [3][n]
+  const float* root_quat;      // [4][n]
+  const float* stones;         // [3 * AS_NUM_STONES][n]
+  const float* rays;           // [6][num_rays] device memory
+  float* hits;                 // [3][num_rays][n]
+  int8_t* surface;             // [num_rays][n] or null
+  float* pose;                 // [7][n] or null
+};
+
 bool step_supported_nv(int nv);
+hipError_t launch_ray_cast(RayArgs a, hipStream_t stream);
 hipError_t launch_contact_timers(const TimersArgs& a, hipStream_t stream);
 hipError_t launch_events_interval(const EventsArgs& a, hipStream_t stream);
 hipError_t launch_events_init(const EventsArgs& a, hipStream_t stream);

@@ -25,8 +25,8 @@
 //   H^-1 sweep -> step_collide.h  contacts -> step_solve.h  rows, PGS, substep -> step_report.h  the opt-in
 //   contact report's stores -> step_task.h  task helpers;
 // after k_step: task_kernels.h (k_obs, k_stones, k_quad), body_state_kernel.h (k_body_state) and
-// contact_forces_kernel.h (k_contact_forces), noise_kernels.h, event_kernels.h and contact_timer_kernels.h
-// (k_contact_timers).
+// contact_forces_kernel.h (k_contact_forces), noise_kernels.h, event_kernels.h, contact_timer_kernels.h
+// (k_contact_timers) and ray_caster_kernels.h (k_ray_cast).
 #include <hip/hip_runtime.h>
 
 #include "../../include/allsteps.h"
@@ -461,6 +461,7 @@ __global__ __launch_bounds__(kStepThreads) __attribute__((amdgpu_waves_per_eu(2,
 #include "noise_kernels.h"
 #include "event_kernels.h"
 #include "contact_timer_kernels.h"
+#include "ray_caster_kernels.h"
 
 namespace as {
 
@@ -549,6 +550,18 @@ hipError_t launch_events_init(const EventsArgs& a, hipStream_t stream) {
 hipError_t launch_contact_timers(const TimersArgs& a, hipStream_t stream) {
   hipLaunchKernelGGL(k_contact_timers, dim3((unsigned)((a.n + kTimerEnvs - 1) / kTimerEnvs)),
                      dim3(kTimerEnvs, kTimerGroup), 0, stream, a);
+  return hipGetLastError();
+}
+
+// kRayEnvs envs x kRayWaves ray slices per workgroup; the slice length: as few rays as give the grid about
+// kRayTargetWaves waves, at least kRayMinChunk (num_rays <= AS_MAX_RAYS: blockIdx.y stays far below its limit)
+hipError_t launch_ray_cast(RayArgs a, hipStream_t stream) {
+  const int env_waves = (a.n + kRayEnvs - 1) / kRayEnvs;
+  const int want = std::max(1, (kRayTargetWaves + env_waves - 1) / env_waves);  // slices per env wave
+  a.chunk = std::max(kRayMinChunk, (a.num_rays + want - 1) / want);
+  const int slices = (a.num_rays + a.chunk - 1) / a.chunk;
+  hipLaunchKernelGGL(k_ray_cast, dim3((unsigned)env_waves, (unsigned)((slices + kRayWaves - 1) / kRayWaves)),
+                     dim3(kRayEnvs, kRayWaves), 0, stream, a, a.rays);
   return hipGetLastError();
 }
 

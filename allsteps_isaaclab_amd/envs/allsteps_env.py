@@ -121,6 +121,7 @@ class AllstepsEnv(NativeDirectEnv):
         """AllstepsEnv._reset_idx(env_ids) (allsteps_env.py:469-567): reset the given envs (curriculum
         gate and second foot-state tick for all envs, as the reference does), then refresh the
         observation buffer.  ``env_ids``: indices, a bool mask, or None (all envs)."""
+        self._scene_changed()
         if env_ids is None:
             obs = self._reset_impl(reset_draws)
             self._sensors_reset(None)
@@ -172,15 +173,18 @@ class AllstepsEnv(NativeDirectEnv):
         the device work of ``step`` but not its Python bookkeeping)."""
         self._sim_step_counter += self.cfg.decimation * k
         self.common_step_counter += k
+        self._scene_changed()
 
     def step_with_draws(self, action: torch.Tensor, reset_draws: torch.Tensor):
         """``step`` with injected reset draws ((N, 22) U[0,1): mirror, 21 joint noise) -- parity tests."""
         self._sim_step_counter += self.cfg.decimation
         out = self._step_impl(action.to(self._device), reset_draws.to(self._device).float().contiguous())
+        self._scene_changed()
         self.common_step_counter += 1
         return out
 
     def reset_with_draws(self, reset_draws: torch.Tensor):
+        self._scene_changed()
         return self._reset_impl(reset_draws.to(self._device).float().contiguous()), self.extras
 
     def task_step(self, action: torch.Tensor, reset_draws: torch.Tensor | None = None):
@@ -190,6 +194,7 @@ class AllstepsEnv(NativeDirectEnv):
         rew = torch.empty(self.num_envs, device=self._device)
         d = None if reset_draws is None else reset_draws.to(self._device).float().contiguous()
         self._native.task_step(a, obs, rew, self.reset_terminated, self.reset_time_outs, d, stream=self._stream())
+        self._scene_changed()
         return {"policy": obs}, rew, self.reset_terminated, self.reset_time_outs, self.extras
 
     def physics_step(self, action: torch.Tensor):
@@ -197,11 +202,13 @@ class AllstepsEnv(NativeDirectEnv):
         a = action.to(self._device).float().contiguous()
         self._native.physics_step(a, stream=self._stream())
         self._launches += 1
+        self._scene_changed()
 
     def generate_foot_steps(self, level: int, draws: torch.Tensor | None = None):
         """_generate_foot_steps_allsteps at `level` for every env (allsteps_env.py:106-174)."""
         d = None if draws is None else draws.to(self._device).float().contiguous()
         self._native.generate_stones(int(level), d, stream=self._stream())
+        self._scene_changed()
 
     def dropped_contacts(self) -> int:
         """Contacts the constraint budget (AS_MAX_CONTACTS contacts, AS_MAX_ROWS rows incl. the joint

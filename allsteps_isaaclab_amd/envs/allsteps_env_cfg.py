@@ -81,6 +81,12 @@ class AllstepsEnvCfg:
     # builds the contact report itself, so the contact_forces views work too.  False: the step as ever.
     contact_air_time: bool = False
     contact_force_threshold: float = 1.0
+    # A ray-caster height scanner on the robot's root body (the reference's RayCasterCfg, e.g. velocity_env_cfg.py:
+    # 66-73): a utils.sensors.RayCasterCfg, or None.  env.height_scanner / env.scene.sensors["height_scanner"] then
+    # cast the cfg's ray pattern against the ground plane and / or the env's stones in one HIP kernel
+    # (csrc/ray_caster_kernels.h) whenever the data is read after the scene changed; mdp.height_scan reads it.  The
+    # step, its observation and the state are as ever either way.  None: nothing allocated, nothing launched.
+    height_scanner: object = None
     # Noise models of DirectRLEnvCfg (direct_rl_env_cfg.py:171, 208): a utils.noise NoiseModelCfg /
     # NoiseModelWithAdditiveBiasCfg (the reference's isaaclab.utils.noise classes) or None.  The action model
     # perturbs the action before the step, the observation model the policy observation after it, a bias model's

@@ -87,6 +87,8 @@ class AnymalCStonesEnvCfg:
     # the four feet's air / contact timers (as AllstepsEnvCfg.contact_air_time / contact_force_threshold)
     contact_air_time: bool = False
     contact_force_threshold: float = 1.0
+    # a ray-caster height scanner on the base (as AllstepsEnvCfg.height_scanner): a utils.sensors.RayCasterCfg or None
+    height_scanner: object = None
     # noise models (as AllstepsEnvCfg's): a utils.noise NoiseModelCfg / NoiseModelWithAdditiveBiasCfg or None
     action_noise_model: object = None
     observation_noise_model: object = None

@@ -28,6 +28,9 @@ class DirectRLEnv:
     # that owns them: an object with update(terminated, truncated) -- the step's sensor updates, then the reset of
     # the envs the step reset -- and reset(mask).  None: step() launches nothing for it.
     _sensors = None
+    # A lazy sensor (the ray-caster height scanner of cfg.height_scanner), set by the subclass that owns it: an
+    # object with mark_dirty().  It is launched by reads of its data, never by step().  None: nothing to mark.
+    height_scanner = None
 
     def __init__(self, cfg, render_mode: str | None = None, **kwargs):
         self.cfg = cfg
@@ -104,6 +107,7 @@ class DirectRLEnv:
             self.seed(seed)
             self._reseed(seed)
         obs = self._reset_impl()
+        self._scene_changed()
         self._sensors_reset(None)
         self._noise_reset(None)  # the returned observation is not noised (direct_rl_env.py:294)
         return obs, self.extras
@@ -124,6 +128,8 @@ class DirectRLEnv:
         if nz is not None and nz.action is not None:
             action = nz.apply_actions(action, self._noise_offset(), self._noise_stream())
         out = self._step_impl(action)
+        if self.height_scanner is not None:  # (an attribute test, as for the events: the default step calls nothing)
+            self.height_scanner.mark_dirty()
         if self._sensors is not None:  # before the events, as a fixed order: the two touch disjoint buffers
             self._sensors.update(out[2], out[3])
         if self._events is not None:
@@ -157,6 +163,13 @@ class DirectRLEnv:
         if self._noise is not None:
             self._noise.set_state(state)
         return {k: v for k, v in state.items() if k not in EnvNoise.STATE_KEYS}
+
+    # ------------------------------------------------------------------ lazy sensors
+    def _scene_changed(self) -> None:
+        """Every path that changes what a lazy sensor sees (root pose, stones) calls this, or does what it does:
+        the sensor is marked outdated (a host flag only: nothing is launched)."""
+        if self.height_scanner is not None:
+            self.height_scanner.mark_dirty()
 
     # ------------------------------------------------------------------ stateful sensors
     def _sensors_reset(self, mask: torch.Tensor | None) -> None:

@@ -9,7 +9,7 @@ import torch
 from .. import _native
 from .direct_rl_env import DirectRLEnv
 from .state import alloc_state
-from .views import _ContactReport, _ContactTimers
+from .views import _ContactReport, _ContactTimers, _RayCaster
 
 
 class NativeDirectEnv(DirectRLEnv):
@@ -22,7 +22,8 @@ class NativeDirectEnv(DirectRLEnv):
         handle over it, seeded with ``cfg.seed``, and the contact report when ``cfg.contact_forces`` (or the
         constructor's override ``contact_forces``) or ``cfg.contact_air_time`` asks for one -- the timers read the
         report, so they bring it (and with it the force views) whether or not the forces were asked for.
-        Env-specific initial values are the caller's."""
+        With ``cfg.height_scanner`` it also builds the ray-caster sensor (``env.height_scanner``,
+        ``env.scene.sensors["height_scanner"]``).  Env-specific initial values are the caller's."""
         dev = self._device
         if dev.type != "cuda" or not torch.cuda.is_available():
             raise _native.NativeError(f"{type(self).__name__} runs on the HIP backend only (device={dev}, HIP device "
@@ -41,6 +42,9 @@ class NativeDirectEnv(DirectRLEnv):
             self._contact_timers = (_ContactTimers(self, self._report, self.cfg.contact_force_threshold)
                                     if air else None)
             self._sensors = self._contact_timers  # DirectRLEnv.step / reset drive them
+            hs = getattr(self.cfg, "height_scanner", None)
+            if hs is not None:  # lazy: launched by reads of its data (or update(force_recompute=True)), never by step
+                self.height_scanner = self.scene.sensors["height_scanner"] = _RayCaster(self, hs)
             self._events_start()
 
     episode_length_buf = property(lambda self: self.state["ep_len"])
@@ -84,6 +88,7 @@ class NativeDirectEnv(DirectRLEnv):
                 **self._events_get_state(), **({} if tm is None else tm.get_state())}
 
     def set_state(self, state: dict):
+        self._scene_changed()
         if self._contact_timers is not None:
             self._contact_timers.set_state(state)
         state = {k: v for k, v in state.items() if k not in _ContactTimers.STATE_KEYS}

@@ -32,10 +32,12 @@ def grid_env_origins(num_envs: int, env_spacing: float, device="cpu") -> torch.T
 
 
 class SceneView:
-    """``env.scene``: ``num_envs``, ``cfg`` and ``env_origins`` (the plane terrain's grid)."""
+    """``env.scene``: ``num_envs``, ``cfg``, ``env_origins`` (the plane terrain's grid) and ``sensors`` -- the
+    sensors an env registers by name (``height_scanner`` with cfg.height_scanner); empty otherwise."""
 
     def __init__(self, cfg, device):
         self.cfg = cfg
+        self.sensors: dict = {}
         self.device = str(device)
         self._origins = None
 

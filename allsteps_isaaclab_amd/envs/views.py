@@ -319,8 +319,89 @@ class _ContactTimers:
                 v.copy_(torch.as_tensor(state[k]).to(v.device, v.dtype).reshape(v.shape))
 
 
+class _RayCasterData:
+    """``RayCasterData`` (ray_caster_data.py): zero-copy strided views of the sensor's env-minor device buffers, as
+    the last launch left them."""
+
+    def __init__(self, sensor: "_RayCaster"):
+        self._s = sensor
+
+    ray_hits_w = property(lambda self: self._s.hits.permute(2, 1, 0))  # (N, R, 3), env-local frame; +inf: a miss
+    pos_w = property(lambda self: self._s.pose[:3].T)  # (N, 3) the root position the rays were cast from
+    quat_w = property(lambda self: self._s.pose[3:].T)  # (N, 4) (w, x, y, z)
+    # extension: (N, R) int8, the stone hit, -1 the ground, -2 a miss
+    ray_hit_surface = property(lambda self: self._s.surface.T)
+
+
+class _RayCaster:
+    """The ray-caster height scanner of an env (``cfg.height_scanner``; the reference's ``RayCaster``,
+    ray_caster.py:201-260, attached to the robot's root body): the local rays of the cfg's pattern and the device
+    buffers of ``as_ray_cast``, which casts them from every env's root frame against the ground plane and the env's
+    stones as they stand.  Lazy like the reference's sensors: reading ``data`` launches only when the env has marked
+    the scene changed since the last launch (``mark_dirty``: step, graph-replay accounting, every reset path,
+    set_state, the robot view's writers, stone regeneration); ``update(force_recompute=True)`` always launches, on
+    the env's current stream -- the call to put inside a captured graph.  The sensor carries no state and draws
+    nothing: no get_state keys, nothing to reset."""
+
+    def __init__(self, env, cfg):
+        from .ray_caster import RayCasterSpec
+
+        n, dev = env.num_envs, env._device
+        root = list(env.model["body_names"])[0]
+        spec = RayCasterSpec(cfg, root_body=root, step_dt=env.step_dt,
+                             step_paths=tuple(getattr(env.cfg, "step_paths", ()) or ()))
+        self._env, self.cfg, self._spec = env, cfg, spec
+        self._native_cfg = spec.native_cfg()
+        self.num_rays = spec.num_rays
+        self.rays = spec.rays.to(dev)  # (6, R): a device tensor, so a captured graph sees later edits
+        self.hits = torch.zeros(3, self.num_rays, n, dtype=torch.float32, device=dev)
+        self.surface = torch.full((self.num_rays, n), _native.RAY_MISS, dtype=torch.int8, device=dev)
+        self.pose = torch.zeros(7, n, dtype=torch.float32, device=dev)
+        self._data = _RayCasterData(self)
+        self._dirty = True
+        self.launches = 0  # as_ray_cast launches so far
+
+    def __str__(self) -> str:
+        n, surfaces = self._env.num_envs, self._spec.surface_names()
+        return (f"Ray-caster @ '{self.cfg.prim_path}': \n"
+                f"\tview type            : {_RobotView}\n"
+                f"\tupdate period (s)    : {self.cfg.update_period}\n"
+                f"\tnumber of meshes     : {len(surfaces)} ({', '.join(surfaces)})\n"
+                f"\tnumber of sensors    : {n}\n"
+                f"\tnumber of rays/sensor: {self.num_rays}\n"
+                f"\ttotal number of rays : {self.num_rays * n}")
+
+    num_instances = property(lambda self: self._env.num_envs)
+    device = property(lambda self: self._env.device)
+
+    def mark_dirty(self) -> None:
+        self._dirty = True
+
+    def _launch(self) -> None:
+        env = self._env
+        env._native.ray_cast(self._native_cfg, self.rays, self.hits, self.surface, self.pose, stream=env._stream())
+        self.launches += 1
+        self._dirty = False
+
+    @property
+    def data(self) -> _RayCasterData:
+        if self._dirty:
+            self._launch()
+        return self._data
+
+    def update(self, dt: float = 0.0, force_recompute: bool = False) -> None:
+        """SensorBase.update: with ``force_recompute`` one launch now; otherwise the next read of ``data`` decides."""
+        if force_recompute:
+            self._launch()
+
+    def reset(self, env_ids=None) -> None:
+        """SensorBase.reset: nothing is kept per env but the outdated flag."""
+        self._dirty = True
+
+
 class _RobotView:
-    """Minimal ``Articulation`` surface: ``data`` plus the state writers used on reset."""
+    """Minimal ``Articulation`` surface: ``data`` plus the state writers used on reset (each tells the env that the
+    scene changed: a lazy sensor recomputes on its next read)."""
 
     def __init__(self, env, default_joint_pos: torch.Tensor | None = None, init_root_pos=None):
         self._env = env
@@ -332,15 +413,18 @@ class _RobotView:
         s = self._env.state
         s["root_pos"][:, ids] = root_pose[:, :3].T.to(s["root_pos"].dtype)
         s["root_quat"][:, ids] = root_pose[:, 3:7].T.to(s["root_quat"].dtype)
+        self._env._scene_changed()
 
     def write_root_velocity_to_sim(self, root_velocity: torch.Tensor, env_ids=None):
         ids = self._ALL_INDICES if env_ids is None else env_ids
         s = self._env.state
         s["root_lin"][:, ids] = root_velocity[:, :3].T.float()
         s["root_ang"][:, ids] = root_velocity[:, 3:6].T.float()
+        self._env._scene_changed()
 
     def write_joint_state_to_sim(self, position, velocity, joint_ids=None, env_ids=None):
         ids = self._ALL_INDICES if env_ids is None else env_ids
         s = self._env.state
         s["q"][:, ids] = position.T.float()
         s["qd"][:, ids] = velocity.T.float()
+        self._env._scene_changed()

@@ -363,6 +363,36 @@ int as_contact_timers(as_env_t* env, const as_body_table_t* bodies_host, float* 
                       float force_threshold, int32_t updates, const uint8_t* reset, const uint8_t* reset2,
                       void* stream);
 
+/* The reference's RayCaster sensor (ray_caster.py:201-260; a height scanner with a grid pattern) over the ground
+ * plane and the env's stones, off by default: one launch of k_ray_cast on `stream` over the state as it stands,
+ * never part of as_step.  One added symbol and one added struct: AS_ABI_VERSION stays 6.
+ *   rays    [6][num_rays]        device memory: local start xyz | direction xyz of every ray, sensor frame
+ *   hits    [3][num_rays][n]     the hit point, env-local frame; (+inf, +inf, +inf) for a miss
+ *   surface int8 [num_rays][n]   the stone hit, AS_RAY_HIT_GROUND or AS_RAY_MISS; may be NULL
+ *   pose    [7][n]               root_pos | root_quat as the kernel read them; may be NULL
+ * The sensor frame is the root link's (root_pos, root_quat).  attach_yaw_only != 0: starts are rotated by the
+ * yaw of root_quat only and directions are the local ones; else both are rotated by root_quat.  Directions are
+ * not normalised: distances, max_distance included, are in units of |direction|.  surfaces selects the ground
+ * plane z = ground_z (hit from above only) and / or the stones, closed boxes stones[3 s .. 3 s + 2] -+
+ * sim.stone_half, s < task.num_steps; a ray from inside a box hits its far face.  The nearest hit with t <=
+ * max_distance wins; on equal t the ground, then the lowest stone (csrc/allsteps_ray_caster.h has the formulas and
+ * the float32 rounding order).  AS_ERR_INVALID, before any device call, for a NULL env / cfg / rays / hits,
+ * num_rays outside [1, 1024 = AS_MAX_RAYS], surfaces 0 or with unknown bits, a max_distance that is not finite
+ * or <= 0, a ground_z that is not finite.  Graph-safe: the rays are read from device memory at every launch. */
+#define AS_RAY_GROUND 1
+#define AS_RAY_STONES 2
+#define AS_RAY_HIT_GROUND (-1)
+#define AS_RAY_MISS (-2)
+typedef struct {
+  int32_t num_rays;
+  int32_t attach_yaw_only;
+  int32_t surfaces;     /* AS_RAY_GROUND | AS_RAY_STONES */
+  float max_distance;
+  float ground_z;
+} as_ray_caster_t;
+int as_ray_cast(as_env_t* env, const as_ray_caster_t* cfg_host, const float* rays, float* hits, int8_t* surface,
+                float* pose, void* stream);
+
 /* Noise models, off by default: DirectRLEnv.step's cfg.action_noise_model / cfg.observation_noise_model
  * (direct_rl_env.py:322-323, 379-380, 578-581; isaaclab/utils/noise/noise_model.py).  Stateless entry points
  * over caller-owned device buffers -- no as_env_t: the env step itself is unchanged, the caller launches
