@@ -27,7 +27,7 @@ EXPORTED_SYMBOLS = [
     "as_profile_sampled", "as_hbm_copy", "as_set_actuator", "as_set_quad_task", "as_quad_step", "as_quad_reset_all",
     "as_build_id", "as_step_counters_host", "as_body_state", "as_sweep_plan", "as_set_contact_report",
     "as_contact_forces", "as_noise_actions", "as_noise_post", "as_events_init", "as_events_interval",
-    "as_contact_timers", "as_ray_cast",
+    "as_contact_timers", "as_ray_cast", "as_imu",
 ]
 MAXB = 32  # AS_MAX_BODIES
 MAXC = 10  # AS_MAX_CONTACTS
@@ -38,6 +38,9 @@ TIMER_ROWS = 4  # as_contact_timers rows: current_air, last_air, current_contact
 MAX_RAYS = 1024  # AS_MAX_RAYS
 RAY_GROUND, RAY_STONES = 1, 2  # AS_RAY_GROUND, AS_RAY_STONES (as_ray_caster_t.surfaces)
 RAY_HIT_GROUND, RAY_MISS = -1, -2  # AS_RAY_HIT_GROUND, AS_RAY_MISS (as_ray_cast's surface)
+MAX_IMUS = 8  # AS_MAX_IMUS
+IMU_DATA_ROWS = 19  # as_imu data rows: pos 3 | quat 4 | lin_vel_b 3 | ang_vel_b 3 | lin_acc_b 3 | ang_acc_b 3
+IMU_PREV_ROWS = 6  # as_imu prev rows: world linear | angular velocity of the previous update
 BODY_STATE_ROWS = 16  # AS_BODY_STATE_ROWS: pos 3 | quat 4 | frame lin vel 3 | ang vel 3 | COM lin vel 3
 
 
@@ -55,6 +58,14 @@ class AsRayCaster(C.Structure):
     """as_ray_caster_t (include/allsteps.h): what one as_ray_cast call casts against and how far."""
     _fields_ = [("num_rays", C.c_int32), ("attach_yaw_only", C.c_int32), ("surfaces", C.c_int32),
                 ("max_distance", C.c_float), ("ground_z", C.c_float)]
+
+
+class AsImuTable(C.Structure):
+    """as_imu_table_t (include/allsteps.h): the sensors of one as_imu call, each on a body of the model."""
+    _fields_ = [("num_sensors", C.c_int32), ("link", C.c_int32 * MAX_IMUS),
+                ("body_offset_pos", (C.c_float * 3) * MAX_IMUS), ("body_offset_quat", (C.c_float * 4) * MAX_IMUS),
+                ("com", (C.c_float * 3) * MAX_IMUS), ("offset_pos", (C.c_float * 3) * MAX_IMUS),
+                ("offset_rot", (C.c_float * 4) * MAX_IMUS), ("gravity_bias", (C.c_float * 3) * MAX_IMUS)]
 
 
 class AsContactReport(C.Structure):
@@ -295,6 +306,7 @@ def load() -> C.CDLL:
     L.as_contact_forces.argtypes = [V, V, V, V, V]
     L.as_contact_timers.argtypes = [V, V, V, V, C.c_float, I32, V, V, V]
     L.as_ray_cast.argtypes = [V, V, V, V, V, V, V]
+    L.as_imu.argtypes = [V, V, C.c_float, I32, V, V, V, V]
     L.as_noise_actions.argtypes = [V, V, V, I32, I32, V, V, U64, I64, V]
     L.as_noise_post.argtypes = [V, V, V, I32, I32, V, V, V, V, V, V, U64, I64, V]
     L.as_events_init.argtypes = [V, I32, V, V, I32, V, U64, I64, V]
@@ -534,6 +546,12 @@ class NativeEnv:
         fp32 [7][n] or None."""
         check(self.L.as_ray_cast(self.h, C.byref(cfg) if cfg is not None else None, _ptr(rays), _ptr(hits),
                                  _ptr(surface), _ptr(pose), stream), "as_ray_cast")
+
+    def imu(self, table: "AsImuTable", dt: float, all_envs: bool, outdated, data, prev, stream=None):
+        """as_imu: the IMU update of every sensor of `table` for the envs flagged in outdated uint8 [n] (all_envs:
+        every env), flags cleared; data fp32 [IMU_DATA_ROWS][S][n], prev fp32 [IMU_PREV_ROWS][S][n]."""
+        check(self.L.as_imu(self.h, C.byref(table) if table is not None else None, dt, int(bool(all_envs)),
+                            _ptr(outdated), _ptr(data), _ptr(prev), stream), "as_imu")
 
     def set_actuator(self, mode: int, action_scale: float = 0.0, default_q=(), stiffness: float = 0.0,
                      damping: float = 0.0, saturation_effort: float = 0.0, effort_limit: float = 0.0,

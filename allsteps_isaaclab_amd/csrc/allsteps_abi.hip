@@ -606,6 +606,38 @@ int as_ray_cast(as_env_t* env, const as_ray_caster_t* cfg_host, const float* ray
   return AS_OK;
 }
 
+int as_imu(as_env_t* env, const as_imu_table_t* host, float dt, int all, uint8_t* outdated, float* data, float* prev,
+           void* stream) {
+  // (what needs no handle is checked first, the handle and what it sizes after)
+  if (!host) return fail(AS_ERR_INVALID, "as_imu: null argument host");
+  if (!outdated) return fail(AS_ERR_INVALID, "as_imu: null argument outdated");
+  if (!data) return fail(AS_ERR_INVALID, "as_imu: null argument data");
+  if (!prev) return fail(AS_ERR_INVALID, "as_imu: null argument prev");
+  const as_imu_table_t& t = *host;
+  if (t.num_sensors < 1 || t.num_sensors > AS_MAX_IMUS)
+    return fail(AS_ERR_INVALID, "as_imu: num_sensors " + std::to_string(t.num_sensors) + " outside [1, AS_MAX_IMUS = " +
+                                    std::to_string(AS_MAX_IMUS) + "]");
+  if (!std::isfinite(dt) || !(dt > 0.f))
+    return fail(AS_ERR_INVALID, "as_imu: dt " + std::to_string(dt) + " is not a finite positive time");
+  if (!env) return fail(AS_ERR_INVALID, "as_imu: null argument env");
+  for (int i = 0; i < t.num_sensors; ++i)
+    if (t.link[i] < 0 || t.link[i] >= env->host.model.num_links)
+      return fail(AS_ERR_INVALID, "as_imu: sensor " + std::to_string(i) + " link " + std::to_string(t.link[i]) +
+                                      " outside the model's " + std::to_string(env->host.model.num_links) + " links");
+  as::ImuArgs a{};
+  a.consts = env->consts_dev;
+  a.st = env->st;
+  a.n = env->n;
+  a.all = all != 0;
+  a.dt = dt;
+  a.outdated = outdated;
+  a.data = data;
+  a.prev = prev;
+  a.imus = t;
+  HIP_TRY(as::launch_imu(a, reinterpret_cast<hipStream_t>(stream)));
+  return AS_OK;
+}
+
 // as_noise_*: a model's ranges and pointers.  `what` names the call and the model in the message.
 static bool noise_model_ok(const as_noise_model_t& m, const std::string& what, std::string& err) {
   if (m.kind < AS_NOISE_CONSTANT || m.kind > AS_NOISE_GAUSSIAN)

@@ -144,6 +144,20 @@ struct BodyArgs {
   as_body_table_t bodies;
 };
 
+// k_imu (as_imu, imu_kernels.h): k_body_state's FK, then the IMU update of every sensor of every outdated env;
+// buffers field-major / env-minor (allsteps_imu.h)
+struct ImuArgs {
+  const Consts* consts;
+  as_state_t st;
+  int32_t n;
+  int32_t all;                 // != 0: treat every env as outdated
+  float dt;
+  uint8_t* outdated;           // [n]
+  float* data;                 // [19][S][n]
+  float* prev;                 // [6][S][n]
+  as_imu_table_t imus;
+};
+
 // k_contact_forces (as_contact_forces): dense sums over the contact report
 struct ForcesArgs {
   int32_t n;
@@ -240,6 +254,7 @@ struct RayArgs {
 
 bool step_supported_nv(int nv);
 hipError_t launch_ray_cast(RayArgs a, hipStream_t stream);
+hipError_t launch_imu(const ImuArgs& a, hipStream_t stream);
 hipError_t launch_contact_timers(const TimersArgs& a, hipStream_t stream);
 hipError_t launch_events_interval(const EventsArgs& a, hipStream_t stream);
 hipError_t launch_events_init(const EventsArgs& a, hipStream_t stream);

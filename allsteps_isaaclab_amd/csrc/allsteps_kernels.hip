@@ -26,7 +26,7 @@
 //   contact report's stores -> step_task.h  task helpers;
 // after k_step: task_kernels.h (k_obs, k_stones, k_quad), body_state_kernel.h (k_body_state) and
 // contact_forces_kernel.h (k_contact_forces), noise_kernels.h, event_kernels.h, contact_timer_kernels.h
-// (k_contact_timers) and ray_caster_kernels.h (k_ray_cast).
+// (k_contact_timers), ray_caster_kernels.h (k_ray_cast) and imu_kernels.h (k_imu).
 #include <hip/hip_runtime.h>
 
 #include "../../include/allsteps.h"
@@ -462,6 +462,7 @@ __global__ __launch_bounds__(kStepThreads) __attribute__((amdgpu_waves_per_eu(2,
 #include "event_kernels.h"
 #include "contact_timer_kernels.h"
 #include "ray_caster_kernels.h"
+#include "imu_kernels.h"
 
 namespace as {
 
@@ -550,6 +551,12 @@ hipError_t launch_events_init(const EventsArgs& a, hipStream_t stream) {
 hipError_t launch_contact_timers(const TimersArgs& a, hipStream_t stream) {
   hipLaunchKernelGGL(k_contact_timers, dim3((unsigned)((a.n + kTimerEnvs - 1) / kTimerEnvs)),
                      dim3(kTimerEnvs, kTimerGroup), 0, stream, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_imu(const ImuArgs& a, hipStream_t stream) {
+  const int blocks = (a.n + EPB - 1) / EPB;
+  hipLaunchKernelGGL(k_imu, dim3(blocks), dim3(kStepThreads), 0, stream, a);
   return hipGetLastError();
 }
 

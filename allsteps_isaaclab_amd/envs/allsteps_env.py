@@ -174,17 +174,21 @@ class AllstepsEnv(NativeDirectEnv):
         self._sim_step_counter += self.cfg.decimation * k
         self.common_step_counter += k
         self._scene_changed()
+        self._time_advanced()
 
     def step_with_draws(self, action: torch.Tensor, reset_draws: torch.Tensor):
         """``step`` with injected reset draws ((N, 22) U[0,1): mirror, 21 joint noise) -- parity tests."""
         self._sim_step_counter += self.cfg.decimation
         out = self._step_impl(action.to(self._device), reset_draws.to(self._device).float().contiguous())
         self._scene_changed()
+        self._time_advanced()
         self.common_step_counter += 1
         return out
 
     def reset_with_draws(self, reset_draws: torch.Tensor):
         self._scene_changed()
+        if self._imus is not None:
+            self._imus.mark(None)
         return self._reset_impl(reset_draws.to(self._device).float().contiguous()), self.extras
 
     def task_step(self, action: torch.Tensor, reset_draws: torch.Tensor | None = None):
@@ -195,6 +199,7 @@ class AllstepsEnv(NativeDirectEnv):
         d = None if reset_draws is None else reset_draws.to(self._device).float().contiguous()
         self._native.task_step(a, obs, rew, self.reset_terminated, self.reset_time_outs, d, stream=self._stream())
         self._scene_changed()
+        self._time_advanced()
         return {"policy": obs}, rew, self.reset_terminated, self.reset_time_outs, self.extras
 
     def physics_step(self, action: torch.Tensor):
@@ -203,6 +208,7 @@ class AllstepsEnv(NativeDirectEnv):
         self._native.physics_step(a, stream=self._stream())
         self._launches += 1
         self._scene_changed()
+        self._time_advanced()
 
     def generate_foot_steps(self, level: int, draws: torch.Tensor | None = None):
         """_generate_foot_steps_allsteps at `level` for every env (allsteps_env.py:106-174)."""

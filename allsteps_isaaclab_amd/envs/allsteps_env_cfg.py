@@ -87,6 +87,12 @@ class AllstepsEnvCfg:
     # (csrc/ray_caster_kernels.h) whenever the data is read after the scene changed; mdp.height_scan reads it.  The
     # step, its observation and the state are as ever either way.  None: nothing allocated, nothing launched.
     height_scanner: object = None
+    # IMU sensors on any of the robot's bodies (the reference's ImuCfg): a utils.sensors.ImuCfg -- then env.imu,
+    # env.scene.sensors["imu"] and the defaults of mdp.imu_orientation / imu_ang_vel / imu_lin_acc -- or a dict of
+    # name -> ImuCfg (at most 8), or None.  One HIP kernel (csrc/imu_kernels.h) updates every sensor of the envs that
+    # are outdated -- all of them after a step or a reset, the envs of a masked reset -- whenever a sensor's data is
+    # read.  The step, its observation and the state are as ever either way.  None: nothing allocated or launched.
+    imu: object = None
     # Noise models of DirectRLEnvCfg (direct_rl_env_cfg.py:171, 208): a utils.noise NoiseModelCfg /
     # NoiseModelWithAdditiveBiasCfg (the reference's isaaclab.utils.noise classes) or None.  The action model
     # perturbs the action before the step, the observation model the policy observation after it, a bias model's

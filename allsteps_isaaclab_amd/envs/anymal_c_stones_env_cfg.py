@@ -89,6 +89,8 @@ class AnymalCStonesEnvCfg:
     contact_force_threshold: float = 1.0
     # a ray-caster height scanner on the base (as AllstepsEnvCfg.height_scanner): a utils.sensors.RayCasterCfg or None
     height_scanner: object = None
+    # IMU sensors on the robot's bodies (as AllstepsEnvCfg.imu): a utils.sensors.ImuCfg, a dict of them, or None
+    imu: object = None
     # noise models (as AllstepsEnvCfg's): a utils.noise NoiseModelCfg / NoiseModelWithAdditiveBiasCfg or None
     action_noise_model: object = None
     observation_noise_model: object = None

@@ -31,6 +31,10 @@ class DirectRLEnv:
     # A lazy sensor (the ray-caster height scanner of cfg.height_scanner), set by the subclass that owns it: an
     # object with mark_dirty().  It is launched by reads of its data, never by step().  None: nothing to mark.
     height_scanner = None
+    # The IMUs of cfg.imu (views._ImuSet), set by the subclass that owns them: lazy like the height scanner, but
+    # outdated by time and by reset only, env by env (a recompute moves their previous velocities).  None: nothing
+    # to mark.
+    _imus = None
 
     def __init__(self, cfg, render_mode: str | None = None, **kwargs):
         self.cfg = cfg
@@ -121,7 +125,8 @@ class DirectRLEnv:
         dones of the firing step are made from values cached before it.  With stateful sensors (the contact
         sensors' air / contact timers): their update for the step's substeps and the reset of the envs the step
         reset (:347, :361) follow the step directly.  Only ``step`` drives them -- a subclass's bare physics or
-        task launches do not."""
+        task launches do not.  With cfg.imu: every env's IMUs become outdated and their ``dt`` the physics step's, as
+        after the reference's sensor updates (:347); nothing is launched until a sensor's data is read."""
         action = action.to(self._device)
         self._sim_step_counter += self.cfg.decimation
         nz = self._noise
@@ -130,6 +135,8 @@ class DirectRLEnv:
         out = self._step_impl(action)
         if self.height_scanner is not None:  # (an attribute test, as for the events: the default step calls nothing)
             self.height_scanner.mark_dirty()
+        if self._imus is not None:  # the step's sensor updates pass physics_dt (direct_rl_env.py:347)
+            self._imus.mark_all(self.physics_dt)
         if self._sensors is not None:  # before the events, as a fixed order: the two touch disjoint buffers
             self._sensors.update(out[2], out[3])
         if self._events is not None:
@@ -171,12 +178,20 @@ class DirectRLEnv:
         if self.height_scanner is not None:
             self.height_scanner.mark_dirty()
 
+    def _time_advanced(self, dt: float | None = None) -> None:
+        """Every path other than ``step`` that advances the simulation (graph-replay accounting, a subclass's bare
+        step launches) calls this: the IMUs are outdated by time, every env (a host flag only)."""
+        if self._imus is not None:
+            self._imus.mark_all(self.physics_dt if dt is None else dt)
+
     # ------------------------------------------------------------------ stateful sensors
     def _sensors_reset(self, mask: torch.Tensor | None) -> None:
         """Sensor.reset(env_ids) for the envs of a uint8 mask (None: all) -- reset() calls it, and the subclass's
         other reset paths after their own reset."""
         if self._sensors is not None:
             self._sensors.reset(mask)
+        if self._imus is not None:  # Imu.reset(env_ids): the envs become outdated, nothing is cleared or launched
+            self._imus.mark(mask)
 
     # ------------------------------------------------------------------ interval events
     def _events_root_velocity(self):

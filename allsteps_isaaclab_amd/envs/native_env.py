@@ -9,7 +9,7 @@ import torch
 from .. import _native
 from .direct_rl_env import DirectRLEnv
 from .state import alloc_state
-from .views import _ContactReport, _ContactTimers, _RayCaster
+from .views import _ContactReport, _ContactTimers, _ImuSet, _RayCaster
 
 
 class NativeDirectEnv(DirectRLEnv):
@@ -23,7 +23,8 @@ class NativeDirectEnv(DirectRLEnv):
         constructor's override ``contact_forces``) or ``cfg.contact_air_time`` asks for one -- the timers read the
         report, so they bring it (and with it the force views) whether or not the forces were asked for.
         With ``cfg.height_scanner`` it also builds the ray-caster sensor (``env.height_scanner``,
-        ``env.scene.sensors["height_scanner"]``).  Env-specific initial values are the caller's."""
+        ``env.scene.sensors["height_scanner"]``), with ``cfg.imu`` the IMUs (``env.scene.sensors[name]``; ``env.imu``
+        for a single cfg).  Env-specific initial values are the caller's."""
         dev = self._device
         if dev.type != "cuda" or not torch.cuda.is_available():
             raise _native.NativeError(f"{type(self).__name__} runs on the HIP backend only (device={dev}, HIP device "
@@ -45,6 +46,15 @@ class NativeDirectEnv(DirectRLEnv):
             hs = getattr(self.cfg, "height_scanner", None)
             if hs is not None:  # lazy: launched by reads of its data (or update(force_recompute=True)), never by step
                 self.height_scanner = self.scene.sensors["height_scanner"] = _RayCaster(self, hs)
+            imu = getattr(self.cfg, "imu", None)
+            if imu is not None:  # lazy too, and one launch serves them all
+                self._imus = _ImuSet(self, imu)
+                taken = sorted(set(self._imus.sensors) & set(self.scene.sensors))
+                if taken:
+                    raise _native.NativeError(f"cfg.imu: the sensor names {taken} are already registered in the scene")
+                self.scene.sensors.update(self._imus.sensors)
+                if not isinstance(imu, dict):
+                    self.imu = self._imus.sensors["imu"]
             self._events_start()
 
     episode_length_buf = property(lambda self: self.state["ep_len"])
@@ -82,16 +92,20 @@ class NativeDirectEnv(DirectRLEnv):
         """Copy of the full SoA state (field -> (rows, N) tensor); with a noise model, also the noise
         stream's counter and biases (noise_t, noise_action_bias, noise_obs_bias); with cfg.events, the event
         streams' counter and timers (event_t, event_time_left); with cfg.contact_air_time, the sensors' timers and
-        timestamp (contact_timers (4, B, N), contact_timestamp (N,))."""
-        tm = self._contact_timers
+        timestamp (contact_timers (4, B, N), contact_timestamp (N,)); with cfg.imu, the IMUs' previous world
+        velocities (imu_prev_lin_vel, imu_prev_ang_vel, (3, S, N) each)."""
+        tm, im = self._contact_timers, self._imus
         return {**{k: v.clone() for k, v in self.state.items()}, **self._noise_get_state(),
-                **self._events_get_state(), **({} if tm is None else tm.get_state())}
+                **self._events_get_state(), **({} if tm is None else tm.get_state()),
+                **({} if im is None else im.get_state())}
 
     def set_state(self, state: dict):
         self._scene_changed()
         if self._contact_timers is not None:
             self._contact_timers.set_state(state)
-        state = {k: v for k, v in state.items() if k not in _ContactTimers.STATE_KEYS}
+        if self._imus is not None:  # (and every env is outdated)
+            self._imus.set_state(state)
+        state = {k: v for k, v in state.items() if k not in _ContactTimers.STATE_KEYS + _ImuSet.STATE_KEYS}
         for k, v in self._events_set_state(self._noise_set_state(state)).items():
             self.state[k].copy_(torch.as_tensor(v).to(self.state[k].device, self.state[k].dtype).reshape(
                 self.state[k].shape))

@@ -33,13 +33,19 @@ def grid_env_origins(num_envs: int, env_spacing: float, device="cpu") -> torch.T
 
 class SceneView:
     """``env.scene``: ``num_envs``, ``cfg``, ``env_origins`` (the plane terrain's grid) and ``sensors`` -- the
-    sensors an env registers by name (``height_scanner`` with cfg.height_scanner); empty otherwise."""
+    sensors an env registers by name (``height_scanner`` with cfg.height_scanner, the IMUs of cfg.imu); empty
+    otherwise.  ``scene[name]`` is the reference's lookup of a scene entity: here, a sensor."""
 
     def __init__(self, cfg, device):
         self.cfg = cfg
         self.sensors: dict = {}
         self.device = str(device)
         self._origins = None
+
+    def __getitem__(self, name: str):
+        if name not in self.sensors:
+            raise KeyError(f"Scene entity with key '{name}' not found. Available Entities: '{list(self.sensors)}'")
+        return self.sensors[name]
 
     @property
     def num_envs(self) -> int:

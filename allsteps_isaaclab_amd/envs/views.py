@@ -399,6 +399,140 @@ class _RayCaster:
         self._dirty = True
 
 
+class _ImuData:
+    """``ImuData`` (imu_data.py) of one sensor: zero-copy strided views of the env-minor device buffer, as the last
+    launch left them.  Positions are env-local, like every other view here (envs/scene.py)."""
+
+    def __init__(self, group: "_ImuSet", s: int):
+        self._g, self._i = group, s
+
+    pos_w = property(lambda self: self._g.data[0:3, self._i].T)  # (N, 3)
+    quat_w = property(lambda self: self._g.data[3:7, self._i].T)  # (N, 4) (w, x, y, z)
+    lin_vel_b = property(lambda self: self._g.data[7:10, self._i].T)  # (N, 3) sensor frame
+    ang_vel_b = property(lambda self: self._g.data[10:13, self._i].T)
+    lin_acc_b = property(lambda self: self._g.data[13:16, self._i].T)
+    ang_acc_b = property(lambda self: self._g.data[16:19, self._i].T)
+
+
+class _Imu:
+    """One IMU of an env (the reference's ``Imu``, imu.py): sensor ``index`` of the env's ``_ImuSet``, which owns
+    the buffers and the launch."""
+
+    STATE_KEYS = ("imu_prev_lin_vel", "imu_prev_ang_vel")
+
+    def __init__(self, group: "_ImuSet", index: int, name: str, cfg):
+        self._g, self.index, self.name, self.cfg = group, index, name, cfg
+        self._data = _ImuData(group, index)
+
+    def __str__(self) -> str:
+        return (f"Imu sensor @ '{self.cfg.prim_path}': \n"
+                f"\tview type         : {_RobotView}\n"
+                f"\tupdate period (s) : {self.cfg.update_period}\n"
+                f"\tnumber of sensors : {self.num_instances}\n")
+
+    num_instances = property(lambda self: self._g._env.num_envs)
+    device = property(lambda self: self._g._env.device)
+    launches = property(lambda self: self._g.launches)  # as_imu launches so far (one serves all the env's IMUs)
+
+    @property
+    def data(self) -> _ImuData:
+        """The sensor's buffers, after one launch if an env is outdated (every env after ``env.step``, graph-replay
+        accounting, ``env.reset()`` and ``set_state``; the envs of a masked reset); a second read launches nothing.
+        The accelerations are the change of velocity since the env's previous update over ``dt`` -- the ``dt`` of
+        the last ``update(dt)``, which ``env.step`` sets to ``physics_dt`` as the reference's does.  So a sensor read
+        once per env step reports the velocity change of the whole env step over ONE physics step: ``decimation``
+        times the step's mean acceleration.  That is the reference's behaviour for this task;
+        ``env.imu.update(env.step_dt, force_recompute=True)`` after each step gives the mean acceleration."""
+        self._g.refresh()
+        return self._data
+
+    def update(self, dt: float, force_recompute: bool = False) -> None:
+        """Imu.update (imu.py:105-109): ``dt`` becomes the divisor of the next updates (of all the env's IMUs: they
+        share the launch); with ``force_recompute`` one launch now, on the env's current stream -- the call to put
+        inside a captured graph -- which recomputes exactly the outdated envs.  Otherwise the next read decides."""
+        self._g.update(dt, force_recompute)
+
+    def reset(self, env_ids=None) -> None:
+        """Imu.reset(env_ids) (imu.py:92-103): the envs become outdated (None: all).  The previous velocities are
+        not cleared, as in the reference; the outdated flag is the env's, shared by its IMUs."""
+        self._g.reset(env_ids)
+
+
+class _ImuSet:
+    """The IMUs of an env (``cfg.imu``): the device buffers of ``as_imu`` (csrc/allsteps_imu.h) and the one launch
+    that serves every sensor.  ``outdated`` is the reference's per-env ``_is_outdated`` on the device; "every env"
+    is a host flag that the launch passes by value (``all``), so marking all envs launches nothing."""
+
+    STATE_KEYS = _Imu.STATE_KEYS
+
+    def __init__(self, env, cfg):
+        from .imu import ImuSpec
+
+        n, dev = env.num_envs, env._device
+        spec = ImuSpec(cfg, model=env.model, step_dt=env.step_dt)
+        self._env, self._spec = env, spec
+        self._table = spec.table()
+        S = self.num_sensors = spec.num_sensors
+        self.data = torch.zeros(_native.IMU_DATA_ROWS, S, n, dtype=torch.float32, device=dev)
+        self.data[3] = 1.0  # quat_w = identity before the first update (imu.py:188-189)
+        self.prev = torch.zeros(_native.IMU_PREV_ROWS, S, n, dtype=torch.float32, device=dev)
+        self.outdated = torch.ones(n, dtype=torch.uint8, device=dev)
+        self.dt = float(env.physics_dt)  # the reference's self._dt: set before the first read (imu.py:145)
+        self._all = self._dirty = True
+        self.launches = 0
+        self.sensors = {name: _Imu(self, s, name, c) for s, (name, c) in enumerate(zip(spec.names, spec.cfgs))}
+
+    def mark_all(self, dt: float | None = None) -> None:
+        """Every env is outdated (a host flag only); ``dt``: the step's ``update(physics_dt)``."""
+        if dt is not None:
+            self.dt = float(dt)
+        self._all = self._dirty = True
+
+    def mark(self, mask: torch.Tensor | None) -> None:
+        """The envs of a uint8 / bool mask are outdated (None: all)."""
+        if mask is None:
+            return self.mark_all()
+        self.outdated.logical_or_(mask)
+        self._dirty = True
+
+    def reset(self, env_ids=None) -> None:
+        if env_ids is None:
+            return self.mark_all()
+        ids = torch.as_tensor(env_ids, device=self.outdated.device)
+        if ids.dtype == torch.bool:
+            return self.mark(ids)
+        self.outdated[ids.long()] = 1
+        self._dirty = True
+
+    def _launch(self) -> None:
+        env = self._env
+        env._native.imu(self._table, self.dt, self._all, self.outdated, self.data, self.prev, stream=env._stream())
+        self.launches += 1
+        self._all = self._dirty = False
+
+    def refresh(self) -> None:
+        if self._dirty:
+            self._launch()
+
+    def update(self, dt: float, force_recompute: bool = False) -> None:
+        self.dt = float(dt)
+        if force_recompute:
+            self._launch()
+
+    # ---- state (get_state / set_state of the envs)
+    def tensors(self) -> dict:
+        return {"imu_prev_lin_vel": self.prev[0:3], "imu_prev_ang_vel": self.prev[3:6]}  # (3, S, N) each
+
+    def get_state(self) -> dict:
+        return {k: v.clone() for k, v in self.tensors().items()}
+
+    def set_state(self, state: dict) -> None:
+        for k, v in self.tensors().items():
+            if k in state:
+                v.copy_(torch.as_tensor(state[k]).to(v.device, v.dtype).reshape(v.shape))
+        self.mark_all()
+
+
 class _RobotView:
     """Minimal ``Articulation`` surface: ``data`` plus the state writers used on reset (each tells the env that the
     scene changed: a lazy sensor recomputes on its next read)."""

@@ -1,8 +1,10 @@
-"""Sensor configuration -- ``RayCasterCfg`` and ``patterns`` of ``isaaclab.sensors`` and the observation function
-``height_scan`` of ``isaaclab.envs.mdp``, same names, fields and defaults, for ``cfg.height_scanner`` of the envs.
+"""Sensor configuration -- ``RayCasterCfg``, ``patterns`` and ``ImuCfg`` of ``isaaclab.sensors`` and the observation
+functions ``height_scan``, ``imu_orientation``, ``imu_ang_vel`` and ``imu_lin_acc`` of ``isaaclab.envs.mdp``, same
+names, fields and defaults, for ``cfg.height_scanner`` and ``cfg.imu`` of the envs.
 
 The rays are cast on the device (``k_ray_cast``, csrc/ray_caster_kernels.h) against the ground plane and the env's
-stones; the env raises at construction for what that kernel does not serve (envs/ray_caster.py).
+stones, and the IMUs are updated on the device (``k_imu``, csrc/imu_kernels.h); the env raises at construction for
+what those kernels do not serve (envs/ray_caster.py, envs/imu.py).
 """
 
 from __future__ import annotations
@@ -11,6 +13,7 @@ from dataclasses import dataclass, field
 from typing import Any
 
 from . import patterns  # noqa: F401  (isaaclab.sensors.patterns)
+from .events import SceneEntityCfg
 from .noise import MISSING
 
 
@@ -41,3 +44,39 @@ def height_scan(env, sensor_cfg, offset: float = 0.5):
     """observations.py ``height_scan``: the sensor's height over every hit point, less ``offset`` -- (N, R)."""
     sensor = env.scene.sensors[sensor_cfg.name]
     return sensor.data.pos_w[:, 2].unsqueeze(1) - sensor.data.ray_hits_w[..., 2] - offset
+
+
+@dataclass
+class ImuCfg:
+    """imu_cfg.py ``ImuCfg`` with ``SensorBaseCfg``'s fields (sensor_base_cfg.py); ``visualizer_cfg`` serves
+    ``debug_vis`` only, which a headless env refuses."""
+
+    @dataclass
+    class OffsetCfg:
+        """The sensor frame's pose in the frame of the body it is attached to."""
+
+        pos: tuple = (0.0, 0.0, 0.0)
+        rot: tuple = (1.0, 0.0, 0.0, 0.0)  # (w, x, y, z)
+
+    prim_path: str = MISSING
+    update_period: float = 0.0
+    history_length: int = 0
+    debug_vis: bool = False
+    offset: OffsetCfg = field(default_factory=OffsetCfg)
+    visualizer_cfg: Any = None
+    gravity_bias: tuple = (0.0, 0.0, 9.81)
+
+
+def imu_orientation(env, asset_cfg: SceneEntityCfg = SceneEntityCfg("imu")):
+    """observations.py ``imu_orientation``: the sensor's orientation in the world frame, (w, x, y, z) -- (N, 4)."""
+    return env.scene[asset_cfg.name].data.quat_w
+
+
+def imu_ang_vel(env, asset_cfg: SceneEntityCfg = SceneEntityCfg("imu")):
+    """observations.py ``imu_ang_vel``: the angular velocity (rad/s) in the sensor frame -- (N, 3)."""
+    return env.scene[asset_cfg.name].data.ang_vel_b
+
+
+def imu_lin_acc(env, asset_cfg: SceneEntityCfg = SceneEntityCfg("imu")):
+    """observations.py ``imu_lin_acc``: the linear acceleration (m/s^2) in the sensor frame -- (N, 3)."""
+    return env.scene[asset_cfg.name].data.lin_acc_b

@@ -393,6 +393,34 @@ typedef struct {
 int as_ray_cast(as_env_t* env, const as_ray_caster_t* cfg_host, const float* rays, float* hits, int8_t* surface,
                 float* pose, void* stream);
 
+/* The reference's Imu sensor (imu.py:142-203) on any body of the model, off by default: one launch of k_imu on
+ * `stream` over the state as it stands, never part of as_step.  One added symbol and one added struct:
+ * AS_ABI_VERSION stays 6.  The launch runs as_body_state's FK, forms each sensor's body row (pose, COM velocities)
+ * and updates the sensors of every outdated env (csrc/allsteps_imu.h has the formulas and the float32 rounding
+ * order); S = num_sensors:
+ *   outdated uint8 [n]    != 0: the env is recomputed and its flag cleared; all != 0 treats every env as set
+ *   data     [19][S][n]   pos_w 3 | quat_w 4 (w, x, y, z) | lin_vel_b 3 | ang_vel_b 3 | lin_acc_b 3 | ang_acc_b 3
+ *   prev     [6][S][n]    the world linear | angular velocity of the env's previous update (zero at first)
+ * An env that is not outdated keeps its data and prev rows bit for bit.  Accelerations are (velocity - prev) / dt,
+ * the linear one plus gravity_bias.  Per sensor: link / body_offset_* / com are the as_body_table_t row of the body
+ * it sits on, offset_pos / offset_rot the sensor frame in that body's frame (offset_rot is used as given).
+ * AS_ERR_INVALID, before any device call, for a NULL env / table / outdated / data / prev, num_sensors outside
+ * [1, AS_MAX_IMUS], a link outside the model, a dt that is not finite or <= 0.  Graph-safe: dt, the table and `all`
+ * are captured by value. */
+#define AS_MAX_IMUS 8
+typedef struct {
+  int32_t num_sensors;
+  int32_t link[AS_MAX_IMUS];              /* the link whose frame carries the sensor's body */
+  float body_offset_pos[AS_MAX_IMUS][3];  /* the body frame in that link's frame (as_body_table_t.offset_pos) */
+  float body_offset_quat[AS_MAX_IMUS][4]; /* (w, x, y, z) */
+  float com[AS_MAX_IMUS][3];              /* the body's own centre of mass, body frame */
+  float offset_pos[AS_MAX_IMUS][3];       /* the sensor frame in the body frame (ImuCfg.offset.pos) */
+  float offset_rot[AS_MAX_IMUS][4];       /* (w, x, y, z), not normalised (ImuCfg.offset.rot) */
+  float gravity_bias[AS_MAX_IMUS][3];     /* added to the world linear acceleration (ImuCfg.gravity_bias) */
+} as_imu_table_t;
+int as_imu(as_env_t* env, const as_imu_table_t* host, float dt, int all, uint8_t* outdated, float* data, float* prev,
+           void* stream);
+
 /* Noise models, off by default: DirectRLEnv.step's cfg.action_noise_model / cfg.observation_noise_model
  * (direct_rl_env.py:322-323, 379-380, 578-581; isaaclab/utils/noise/noise_model.py).  Stateless entry points
  * over caller-owned device buffers -- no as_env_t: the env step itself is unchanged, the caller launches
