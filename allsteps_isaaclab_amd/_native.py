@@ -27,7 +27,7 @@ EXPORTED_SYMBOLS = [
     "as_profile_sampled", "as_hbm_copy", "as_set_actuator", "as_set_quad_task", "as_quad_step", "as_quad_reset_all",
     "as_build_id", "as_step_counters_host", "as_body_state", "as_sweep_plan", "as_set_contact_report",
     "as_contact_forces", "as_noise_actions", "as_noise_post", "as_events_init", "as_events_interval",
-    "as_contact_timers", "as_ray_cast", "as_imu",
+    "as_contact_timers", "as_ray_cast", "as_imu", "as_ray_camera",
 ]
 MAXB = 32  # AS_MAX_BODIES
 MAXC = 10  # AS_MAX_CONTACTS
@@ -38,6 +38,8 @@ TIMER_ROWS = 4  # as_contact_timers rows: current_air, last_air, current_contact
 MAX_RAYS = 1024  # AS_MAX_RAYS
 RAY_GROUND, RAY_STONES = 1, 2  # AS_RAY_GROUND, AS_RAY_STONES (as_ray_caster_t.surfaces)
 RAY_HIT_GROUND, RAY_MISS = -1, -2  # AS_RAY_HIT_GROUND, AS_RAY_MISS (as_ray_cast's surface)
+MAX_CAMERA_RAYS = 16384  # AS_MAX_CAMERA_RAYS (128 x 128)
+CAM_CLIP_NONE, CAM_CLIP_MAX, CAM_CLIP_ZERO = 0, 1, 2  # AS_CAM_CLIP_* (as_ray_camera_t.clipping)
 MAX_IMUS = 8  # AS_MAX_IMUS
 IMU_DATA_ROWS = 19  # as_imu data rows: pos 3 | quat 4 | lin_vel_b 3 | ang_vel_b 3 | lin_acc_b 3 | ang_acc_b 3
 IMU_PREV_ROWS = 6  # as_imu prev rows: world linear | angular velocity of the previous update
@@ -57,6 +59,12 @@ class AsBodyTable(C.Structure):
 class AsRayCaster(C.Structure):
     """as_ray_caster_t (include/allsteps.h): what one as_ray_cast call casts against and how far."""
     _fields_ = [("num_rays", C.c_int32), ("attach_yaw_only", C.c_int32), ("surfaces", C.c_int32),
+                ("max_distance", C.c_float), ("ground_z", C.c_float)]
+
+
+class AsRayCamera(C.Structure):
+    """as_ray_camera_t (include/allsteps.h): the image, what one as_ray_camera call casts against and the clipping."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("surfaces", C.c_int32), ("clipping", C.c_int32),
                 ("max_distance", C.c_float), ("ground_z", C.c_float)]
 
 
@@ -307,6 +315,7 @@ def load() -> C.CDLL:
     L.as_contact_timers.argtypes = [V, V, V, V, C.c_float, I32, V, V, V]
     L.as_ray_cast.argtypes = [V, V, V, V, V, V, V]
     L.as_imu.argtypes = [V, V, C.c_float, I32, V, V, V, V]
+    L.as_ray_camera.argtypes = [V, V, V, V, V, V, V, V, V]
     L.as_noise_actions.argtypes = [V, V, V, I32, I32, V, V, U64, I64, V]
     L.as_noise_post.argtypes = [V, V, V, I32, I32, V, V, V, V, V, V, U64, I64, V]
     L.as_events_init.argtypes = [V, I32, V, V, I32, V, U64, I64, V]
@@ -546,6 +555,13 @@ class NativeEnv:
         fp32 [7][n] or None."""
         check(self.L.as_ray_cast(self.h, C.byref(cfg) if cfg is not None else None, _ptr(rays), _ptr(hits),
                                  _ptr(surface), _ptr(pose), stream), "as_ray_cast")
+
+    def ray_camera(self, cfg: "AsRayCamera", dirs, offset, pose, plane=None, camera=None, normals=None, stream=None):
+        """as_ray_camera: the pixels' local directions fp32 [3][R] and the per-env offsets fp32 [7][n] (device) from
+        every env's root frame against the ground and the stones; writes pose [7][n] and the images that are not
+        None -- plane, camera [n][R], normals [n][R][3], env-major -- one launch on `stream`."""
+        check(self.L.as_ray_camera(self.h, C.byref(cfg) if cfg is not None else None, _ptr(dirs), _ptr(offset),
+                                   _ptr(pose), _ptr(plane), _ptr(camera), _ptr(normals), stream), "as_ray_camera")
 
     def imu(self, table: "AsImuTable", dt: float, all_envs: bool, outdated, data, prev, stream=None):
         """as_imu: the IMU update of every sensor of `table` for the envs flagged in outdated uint8 [n] (all_envs:

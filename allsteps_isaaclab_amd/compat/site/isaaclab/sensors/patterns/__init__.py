@@ -1,5 +1,7 @@
-"""Shim of ``isaaclab.sensors.patterns``: the grid pattern of the ray-caster sensor."""
+"""Shim of ``isaaclab.sensors.patterns``: the grid pattern of the ray-caster sensor and the pinhole pattern of the
+ray-cast camera."""
 
-from allsteps_isaaclab_amd.utils.patterns import GridPatternCfg, PatternBaseCfg, grid_pattern  # noqa: F401
+from allsteps_isaaclab_amd.utils.patterns import (  # noqa: F401
+    GridPatternCfg, PatternBaseCfg, PinholeCameraPatternCfg, grid_pattern, pinhole_camera_pattern)
 
-__all__ = ["GridPatternCfg", "PatternBaseCfg", "grid_pattern"]
+__all__ = ["GridPatternCfg", "PatternBaseCfg", "PinholeCameraPatternCfg", "grid_pattern", "pinhole_camera_pattern"]

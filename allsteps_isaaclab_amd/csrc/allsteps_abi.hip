@@ -13,6 +13,7 @@
 #include "allsteps_kernels.h"
 #include "allsteps_events.h"
 #include "allsteps_noise.h"
+#include "allsteps_ray_camera.h"
 #include "allsteps_ray_caster.h"
 
 namespace {
@@ -603,6 +604,54 @@ int as_ray_cast(as_env_t* env, const as_ray_caster_t* cfg_host, const float* ray
   a.surface = surface;
   a.pose = pose;
   HIP_TRY(as::launch_ray_cast(a, reinterpret_cast<hipStream_t>(stream)));
+  return AS_OK;
+}
+
+int as_ray_camera(as_env_t* env, const as_ray_camera_t* cfg_host, const float* dirs, const float* offset,
+                  float* pose, float* plane, float* camera, float* normals, void* stream) {
+  // (what needs no handle is checked first, the handle after)
+  if (!cfg_host) return fail(AS_ERR_INVALID, "as_ray_camera: null argument cfg");
+  if (!dirs) return fail(AS_ERR_INVALID, "as_ray_camera: null argument dirs");
+  if (!offset) return fail(AS_ERR_INVALID, "as_ray_camera: null argument offset");
+  if (!pose) return fail(AS_ERR_INVALID, "as_ray_camera: null argument pose");
+  if (!plane && !camera && !normals)
+    return fail(AS_ERR_INVALID, "as_ray_camera: plane, camera and normals are all null: no data type is requested");
+  const as_ray_camera_t& c = *cfg_host;
+  if (c.width < 1 || c.height < 1 || (int64_t)c.width * (int64_t)c.height > AS_MAX_CAMERA_RAYS)
+    return fail(AS_ERR_INVALID, "as_ray_camera: image " + std::to_string(c.width) + " x " + std::to_string(c.height) +
+                                    " is not positive with at most AS_MAX_CAMERA_RAYS = " +
+                                    std::to_string(AS_MAX_CAMERA_RAYS) + " pixels");
+  if (c.surfaces == 0 || (c.surfaces & ~as::kRaySurfAll))
+    return fail(AS_ERR_INVALID, "as_ray_camera: surfaces " + std::to_string(c.surfaces) +
+                                    " is not AS_RAY_GROUND, AS_RAY_STONES or both");
+  if (c.clipping != AS_CAM_CLIP_NONE && c.clipping != AS_CAM_CLIP_MAX && c.clipping != AS_CAM_CLIP_ZERO)
+    return fail(AS_ERR_INVALID, "as_ray_camera: clipping " + std::to_string(c.clipping) +
+                                    " is not AS_CAM_CLIP_NONE, AS_CAM_CLIP_MAX or AS_CAM_CLIP_ZERO");
+  if (!std::isfinite(c.max_distance) || !(c.max_distance > 0.f))
+    return fail(AS_ERR_INVALID, "as_ray_camera: max_distance " + std::to_string(c.max_distance) +
+                                    " is not a finite positive distance");
+  if (!std::isfinite(c.ground_z))
+    return fail(AS_ERR_INVALID, "as_ray_camera: ground_z " + std::to_string(c.ground_z) + " is not finite");
+  if (!env) return fail(AS_ERR_INVALID, "as_ray_camera: null argument env");
+  as::CamArgs a{};
+  a.n = env->n;
+  a.num_rays = c.width * c.height;
+  a.surfaces = c.surfaces;
+  a.clipping = c.clipping;
+  a.num_steps = env->host.task.num_steps;
+  a.max_distance = c.max_distance;
+  a.ground_z = c.ground_z;
+  for (int k = 0; k < 3; ++k) a.half[k] = env->host.sim.stone_half[k];
+  a.root_pos = env->st.root_pos;
+  a.root_quat = env->st.root_quat;
+  a.stones = env->st.stones;
+  a.dirs = dirs;
+  a.offset = offset;
+  a.pose = pose;
+  a.plane = plane;
+  a.camera = camera;
+  a.normals = normals;
+  HIP_TRY(as::launch_ray_camera(a, reinterpret_cast<hipStream_t>(stream)));
   return AS_OK;
 }
 

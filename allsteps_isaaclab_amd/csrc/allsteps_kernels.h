@@ -252,8 +252,30 @@ struct RayArgs {
   float* pose;                 // [7][n] or null
 };
 
+// k_ray_camera (as_ray_camera, ray_camera_kernels.h): the depth camera's pixels against the ground and the stones;
+// inputs env-minor, images env-major (allsteps_ray_camera.h)
+struct CamArgs {
+  int32_t n;
+  int32_t num_rays;            // width * height
+  int32_t surfaces;            // AS_RAY_GROUND | AS_RAY_STONES
+  int32_t clipping;            // AS_CAM_CLIP_*
+  int32_t num_steps;           // stones per env
+  float max_distance, ground_z;
+  float half[3];               // sim.stone_half
+  const float* root_pos;       // [3][n]
+  const float* root_quat;      // [4][n]
+  const float* stones;         // [3 * AS_NUM_STONES][n]
+  const float* dirs;           // [3][num_rays] device memory
+  const float* offset;         // [7][n] device memory
+  float* pose;                 // [7][n]
+  float* plane;                // [n][num_rays] or null
+  float* camera;               // [n][num_rays] or null
+  float* normals;              // [n][num_rays][3] or null
+};
+
 bool step_supported_nv(int nv);
 hipError_t launch_ray_cast(RayArgs a, hipStream_t stream);
+hipError_t launch_ray_camera(const CamArgs& a, hipStream_t stream);
 hipError_t launch_imu(const ImuArgs& a, hipStream_t stream);
 hipError_t launch_contact_timers(const TimersArgs& a, hipStream_t stream);
 hipError_t launch_events_interval(const EventsArgs& a, hipStream_t stream);

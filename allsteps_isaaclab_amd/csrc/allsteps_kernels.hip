@@ -26,7 +26,8 @@
 //   contact report's stores -> step_task.h  task helpers;
 // after k_step: task_kernels.h (k_obs, k_stones, k_quad), body_state_kernel.h (k_body_state) and
 // contact_forces_kernel.h (k_contact_forces), noise_kernels.h, event_kernels.h, contact_timer_kernels.h
-// (k_contact_timers), ray_caster_kernels.h (k_ray_cast) and imu_kernels.h (k_imu).
+// (k_contact_timers), ray_caster_kernels.h (k_ray_cast), imu_kernels.h (k_imu) and ray_camera_kernels.h
+// (k_ray_camera).
 #include <hip/hip_runtime.h>
 
 #include "../../include/allsteps.h"
@@ -463,6 +464,7 @@ __global__ __launch_bounds__(kStepThreads) __attribute__((amdgpu_waves_per_eu(2,
 #include "contact_timer_kernels.h"
 #include "ray_caster_kernels.h"
 #include "imu_kernels.h"
+#include "ray_camera_kernels.h"
 
 namespace as {
 
@@ -569,6 +571,15 @@ hipError_t launch_ray_cast(RayArgs a, hipStream_t stream) {
   const int slices = (a.num_rays + a.chunk - 1) / a.chunk;
   hipLaunchKernelGGL(k_ray_cast, dim3((unsigned)env_waves, (unsigned)((slices + kRayWaves - 1) / kRayWaves)),
                      dim3(kRayEnvs, kRayWaves), 0, stream, a, a.rays);
+  return hipGetLastError();
+}
+
+// one env x kCamTile pixels per workgroup; envs over grid y and z (num_rays <= AS_MAX_CAMERA_RAYS: at most 64 tiles)
+hipError_t launch_ray_camera(const CamArgs& a, hipStream_t stream) {
+  const int tiles = (a.num_rays + kCamTile - 1) / kCamTile;
+  const int ey = std::min(a.n, kCamGridY), ez = (a.n + kCamGridY - 1) / kCamGridY;
+  hipLaunchKernelGGL(k_ray_camera, dim3((unsigned)tiles, (unsigned)ey, (unsigned)ez), dim3(kCamTile), 0, stream, a,
+                     a.root_pos, a.root_quat, a.stones, a.offset, a.dirs);
   return hipGetLastError();
 }
 

@@ -93,6 +93,11 @@ class AllstepsEnvCfg:
     # are outdated -- all of them after a step or a reset, the envs of a masked reset -- whenever a sensor's data is
     # read.  The step, its observation and the state are as ever either way.  None: nothing allocated or launched.
     imu: object = None
+    # ray-cast depth cameras on the root body (the reference's RayCasterCameraCfg): a utils.sensors.RayCasterCameraCfg
+    # -- then env.camera and env.scene.sensors["camera"] -- or a dict of name -> cfg (at most 4), or None.  One HIP
+    # kernel (csrc/ray_camera_kernels.h) casts a camera's pixels against the ground and the stones whenever its data
+    # is read after the scene changed; mdp.image reads it.  The default step launches nothing for it.
+    camera: object = None
     # Noise models of DirectRLEnvCfg (direct_rl_env_cfg.py:171, 208): a utils.noise NoiseModelCfg /
     # NoiseModelWithAdditiveBiasCfg (the reference's isaaclab.utils.noise classes) or None.  The action model
     # perturbs the action before the step, the observation model the policy observation after it, a bias model's

@@ -91,6 +91,11 @@ class AnymalCStonesEnvCfg:
     height_scanner: object = None
     # IMU sensors on the robot's bodies (as AllstepsEnvCfg.imu): a utils.sensors.ImuCfg, a dict of them, or None
     imu: object = None
+    # ray-cast depth cameras on the root body (the reference's RayCasterCameraCfg): a utils.sensors.RayCasterCameraCfg
+    # -- then env.camera and env.scene.sensors["camera"] -- or a dict of name -> cfg (at most 4), or None.  One HIP
+    # kernel (csrc/ray_camera_kernels.h) casts a camera's pixels against the ground and the stones whenever its data
+    # is read after the scene changed; mdp.image reads it.  The default step launches nothing for it.
+    camera: object = None
     # noise models (as AllstepsEnvCfg's): a utils.noise NoiseModelCfg / NoiseModelWithAdditiveBiasCfg or None
     action_noise_model: object = None
     observation_noise_model: object = None

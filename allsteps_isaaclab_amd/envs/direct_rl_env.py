@@ -31,6 +31,11 @@ class DirectRLEnv:
     # A lazy sensor (the ray-caster height scanner of cfg.height_scanner), set by the subclass that owns it: an
     # object with mark_dirty().  It is launched by reads of its data, never by step().  None: nothing to mark.
     height_scanner = None
+    # Every lazy sensor of the env -- the height scanner and the ray-cast cameras of cfg.camera -- as the subclass
+    # that owns them registered them (_add_lazy_sensor): objects with mark_dirty().  Empty: nothing to mark.
+    _lazy_sensors: tuple = ()
+    # The cameras among them (views._RayCasterCamera): a reset also zeroes their frame counters.  Empty: none.
+    _cameras: tuple = ()
     # The IMUs of cfg.imu (views._ImuSet), set by the subclass that owns them: lazy like the height scanner, but
     # outdated by time and by reset only, env by env (a recompute moves their previous velocities).  None: nothing
     # to mark.
@@ -133,8 +138,8 @@ class DirectRLEnv:
         if nz is not None and nz.action is not None:
             action = nz.apply_actions(action, self._noise_offset(), self._noise_stream())
         out = self._step_impl(action)
-        if self.height_scanner is not None:  # (an attribute test, as for the events: the default step calls nothing)
-            self.height_scanner.mark_dirty()
+        for sensor in self._lazy_sensors:  # (empty by default: the default step calls nothing)
+            sensor.mark_dirty()
         if self._imus is not None:  # the step's sensor updates pass physics_dt (direct_rl_env.py:347)
             self._imus.mark_all(self.physics_dt)
         if self._sensors is not None:  # before the events, as a fixed order: the two touch disjoint buffers
@@ -172,11 +177,16 @@ class DirectRLEnv:
         return {k: v for k, v in state.items() if k not in EnvNoise.STATE_KEYS}
 
     # ------------------------------------------------------------------ lazy sensors
+    def _add_lazy_sensor(self, sensor, camera: bool = False) -> None:
+        self._lazy_sensors = (*self._lazy_sensors, sensor)
+        if camera:
+            self._cameras = (*self._cameras, sensor)
+
     def _scene_changed(self) -> None:
         """Every path that changes what a lazy sensor sees (root pose, stones) calls this, or does what it does:
-        the sensor is marked outdated (a host flag only: nothing is launched)."""
-        if self.height_scanner is not None:
-            self.height_scanner.mark_dirty()
+        the sensors are marked outdated (a host flag only: nothing is launched)."""
+        for sensor in self._lazy_sensors:
+            sensor.mark_dirty()
 
     def _time_advanced(self, dt: float | None = None) -> None:
         """Every path other than ``step`` that advances the simulation (graph-replay accounting, a subclass's bare
@@ -192,6 +202,8 @@ class DirectRLEnv:
             self._sensors.reset(mask)
         if self._imus is not None:  # Imu.reset(env_ids): the envs become outdated, nothing is cleared or launched
             self._imus.mark(mask)
+        for camera in self._cameras:  # RayCasterCamera.reset(env_ids): the envs' frame counters become zero
+            camera.reset(None if mask is None else mask.bool())
 
     # ------------------------------------------------------------------ interval events
     def _events_root_velocity(self):

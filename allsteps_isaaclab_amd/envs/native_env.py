@@ -9,7 +9,7 @@ import torch
 from .. import _native
 from .direct_rl_env import DirectRLEnv
 from .state import alloc_state
-from .views import _ContactReport, _ContactTimers, _ImuSet, _RayCaster
+from .views import _ContactReport, _ContactTimers, _ImuSet, _RayCaster, _RayCasterCamera
 
 
 class NativeDirectEnv(DirectRLEnv):
@@ -23,7 +23,8 @@ class NativeDirectEnv(DirectRLEnv):
         constructor's override ``contact_forces``) or ``cfg.contact_air_time`` asks for one -- the timers read the
         report, so they bring it (and with it the force views) whether or not the forces were asked for.
         With ``cfg.height_scanner`` it also builds the ray-caster sensor (``env.height_scanner``,
-        ``env.scene.sensors["height_scanner"]``), with ``cfg.imu`` the IMUs (``env.scene.sensors[name]``; ``env.imu``
+        ``env.scene.sensors["height_scanner"]``), with ``cfg.camera`` the ray-cast cameras (``env.scene.sensors[name]``;
+        ``env.camera`` for a single cfg), with ``cfg.imu`` the IMUs (``env.scene.sensors[name]``; ``env.imu``
         for a single cfg).  Env-specific initial values are the caller's."""
         dev = self._device
         if dev.type != "cuda" or not torch.cuda.is_available():
@@ -46,6 +47,21 @@ class NativeDirectEnv(DirectRLEnv):
             hs = getattr(self.cfg, "height_scanner", None)
             if hs is not None:  # lazy: launched by reads of its data (or update(force_recompute=True)), never by step
                 self.height_scanner = self.scene.sensors["height_scanner"] = _RayCaster(self, hs)
+                self._add_lazy_sensor(self.height_scanner)
+            cam = getattr(self.cfg, "camera", None)
+            if cam is not None:  # lazy as well; each camera has its own buffers and its own launch
+                from .ray_camera import named_cfgs
+
+                cams = named_cfgs(cam)
+                taken = sorted(set(cams) & set(self.scene.sensors))
+                if taken:
+                    raise _native.NativeError(f"cfg.camera: the sensor names {taken} are already registered in the "
+                                              f"scene")
+                for name, c in cams.items():
+                    self.scene.sensors[name] = _RayCasterCamera(self, c, name)
+                    self._add_lazy_sensor(self.scene.sensors[name], camera=True)
+                if not isinstance(cam, dict):
+                    self.camera = self.scene.sensors["camera"]
             imu = getattr(self.cfg, "imu", None)
             if imu is not None:  # lazy too, and one launch serves them all
                 self._imus = _ImuSet(self, imu)

@@ -399,6 +399,170 @@ class _RayCaster:
         self._dirty = True
 
 
+class _CameraData:
+    """``CameraData`` (camera_data.py) of a ray-cast camera: views of the sensor's device buffers, as the last launch
+    left them.  Positions are env-local, like every other view here (envs/scene.py)."""
+
+    def __init__(self, sensor: "_RayCasterCamera"):
+        self._s = sensor
+        self.image_shape = sensor.image_shape
+        h, w = sensor.image_shape
+        # (N, H, W, C): zero-copy views of the env-major buffers
+        self.output = {name: buf.view(-1, h, w, 3 if name == "normals" else 1) for name, buf in sensor.images.items()}
+        self.info = [{name: None for name in sensor.images}] * sensor.num_instances
+
+    pos_w = property(lambda self: self._s.pose[:3].T)  # (N, 3) the camera's position
+    quat_w_world = property(lambda self: self._s.pose[3:].T)  # (N, 4) (w, x, y, z), forward +X, up +Z
+    intrinsic_matrices = property(lambda self: self._s.intrinsic_matrices)  # (N, 3, 3)
+
+    @property
+    def quat_w_ros(self) -> torch.Tensor:
+        """(N, 4) the orientation in the ROS convention (forward +Z, up -Y): torch on the device."""
+        from .ray_camera import quat_from_world_torch
+
+        return quat_from_world_torch(self.quat_w_world, "ros")
+
+    @property
+    def quat_w_opengl(self) -> torch.Tensor:
+        """(N, 4) the orientation in the OpenGL / USD convention (forward -Z, up +Y): torch on the device."""
+        from .ray_camera import quat_from_world_torch
+
+        return quat_from_world_torch(self.quat_w_world, "opengl")
+
+
+class _RayCasterCamera:
+    """A ray-cast depth camera of an env (``cfg.camera``; the reference's ``RayCasterCamera``,
+    ray_caster_camera.py, attached to the robot's root body): the pixels' local directions, the per-env offsets and
+    the device buffers of ``as_ray_camera``, which casts them from every env's camera pose against the ground plane
+    and the env's stones as they stand and writes the requested images env-major.  Lazy like the height scanner:
+    reading ``data`` launches only when the env has marked the scene changed since the last launch (``mark_dirty``:
+    step, graph-replay accounting, every reset path, set_state, the robot view's writers, stone regeneration) or
+    the camera itself was moved or re-focused; ``update(force_recompute=True)`` always launches, on the env's
+    current stream -- the call to put inside a captured graph.  No get_state keys: the images are a function of the
+    state, the offsets and intrinsics are configuration.
+
+    ``frame`` counts launches per env and ``reset(env_ids)`` zeroes it for those envs.  One deviation from the
+    reference: after a masked reset that follows a read in the same step the reference recomputes and counts only
+    the reset envs; here every env is recomputed (the same state gives the same bits) and every env's count moves."""
+
+    def __init__(self, env, cfg, name: str = "camera"):
+        from .ray_camera import RayCameraSpec
+
+        n, dev = env.num_envs, env._device
+        root = list(env.model["body_names"])[0]
+        spec = RayCameraSpec(cfg, root_body=root, step_dt=env.step_dt,
+                             step_paths=tuple(getattr(env.cfg, "step_paths", ()) or ()), name=name)
+        self._env, self.cfg, self._spec, self.name = env, cfg, spec, name
+        self._native_cfg = spec.native_cfg()
+        self.num_rays = R = spec.num_rays
+        self.image_shape = (spec.height, spec.width)
+        # device tensors, so a captured graph sees later set_world_poses / set_intrinsic_matrices edits
+        self.dirs = torch.from_numpy(spec.dirs).to(dev)  # (3, R)
+        self.offset = torch.from_numpy(spec.offset).to(dev).reshape(7, 1).repeat(1, n).contiguous()  # (7, N)
+        self.intrinsic_matrices = torch.from_numpy(spec.intrinsics).to(dev).repeat(n, 1, 1)  # (N, 3, 3)
+        self.pose = torch.zeros(7, n, dtype=torch.float32, device=dev)
+        self.images = {t: torch.zeros(n, R, 3 if t == "normals" else 1, dtype=torch.float32, device=dev)
+                       for t in spec.data_types}
+        self.frame = torch.zeros(n, dtype=torch.long, device=dev)
+        self._ALL_INDICES = torch.arange(n, dtype=torch.long, device=dev)
+        self._focal_length = spec.pattern.focal_length
+        self._data = _CameraData(self)
+        self._dirty = True
+        self.launches = 0  # as_ray_camera launches so far
+
+    def __str__(self) -> str:
+        n, surfaces = self._env.num_envs, self._spec.surface_names()
+        return (f"Ray-Caster-Camera @ '{self.cfg.prim_path}': \n"
+                f"\tview type            : {_RobotView}\n"
+                f"\tupdate period (s)    : {self.cfg.update_period}\n"
+                f"\tnumber of meshes     : {len(surfaces)} ({', '.join(surfaces)})\n"
+                f"\tnumber of sensors    : {n}\n"
+                f"\tnumber of rays/sensor: {self.num_rays}\n"
+                f"\ttotal number of rays : {self.num_rays * n}\n"
+                f"\timage shape          : {self.image_shape}")
+
+    num_instances = property(lambda self: self._env.num_envs)
+    device = property(lambda self: self._env.device)
+
+    def mark_dirty(self) -> None:
+        self._dirty = True
+
+    def _launch(self) -> None:
+        env, im = self._env, self.images
+        env._native.ray_camera(self._native_cfg, self.dirs, self.offset, self.pose, im.get("distance_to_image_plane"),
+                               im.get("distance_to_camera"), im.get("normals"), stream=env._stream())
+        self.frame += 1  # on the current stream as well: capturable
+        self.launches += 1
+        self._dirty = False
+
+    @property
+    def data(self) -> _CameraData:
+        if self._dirty:
+            self._launch()
+        return self._data
+
+    def update(self, dt: float = 0.0, force_recompute: bool = False) -> None:
+        """SensorBase.update: with ``force_recompute`` one launch now; otherwise the next read of ``data`` decides."""
+        if force_recompute:
+            self._launch()
+
+    def reset(self, env_ids=None) -> None:
+        """RayCasterCamera.reset (ray_caster_camera.py:142-154): the frame count of the envs becomes zero and the
+        sensor outdated; the pose rows are rewritten by the next launch, before they can be read."""
+        if env_ids is None:
+            self.frame.zero_()
+        else:
+            ids = torch.as_tensor(env_ids, device=self.frame.device)
+            if ids.dtype == torch.bool:
+                self.frame.masked_fill_(ids, 0)
+            else:
+                self.frame[ids.long()] = 0
+        self._dirty = True
+
+    def set_intrinsic_matrices(self, matrices: torch.Tensor, focal_length: float = 1.0, env_ids=None) -> None:
+        """ray_caster_camera.py:121-140, for all envs at once with equal matrices -- the kernel takes one table of
+        directions: ``matrices`` is (3, 3) or (N, 3, 3) with N equal rows.  Rewrites the device directions in
+        place."""
+        m = torch.as_tensor(matrices, dtype=torch.float32).detach().cpu()
+        n = self._env.num_envs
+        if env_ids is not None and sorted(int(i) for i in torch.as_tensor(env_ids).reshape(-1).tolist()) \
+                != list(range(n)):
+            raise _native.NativeError("camera.set_intrinsic_matrices: env_ids selects some of the envs; per-env "
+                                      "intrinsics are not served (one HIP launch takes one table of ray directions)")
+        if m.shape == (3, 3):
+            m = m.reshape(1, 3, 3)
+        if m.ndim != 3 or m.shape[1:] != (3, 3) or m.shape[0] not in (1, n) or bool((m != m[:1]).any()):
+            raise _native.NativeError(f"camera.set_intrinsic_matrices: matrices of shape {tuple(m.shape)} are not one "
+                                      f"(3, 3) matrix or ({n}, 3, 3) equal ones; per-env intrinsics are not served "
+                                      f"(one HIP launch takes one table of ray directions)")
+        dirs = self._spec.directions(m[0].numpy())
+        self.dirs.copy_(torch.from_numpy(dirs))
+        self.intrinsic_matrices.copy_(m[:1].to(self.intrinsic_matrices.device).expand(n, 3, 3))
+        self._focal_length = focal_length
+        self._dirty = True
+
+    def set_world_poses(self, positions=None, orientations=None, env_ids=None, convention: str = "ros") -> None:
+        """ray_caster_camera.py:156-206: place the cameras of ``env_ids`` in the world (env-local frame) by rewriting
+        their offsets against the root poses as they stand; torch on the device."""
+        from .ray_camera import world_pose_offsets
+
+        dev = self.offset.device
+        ids = self._ALL_INDICES if env_ids is None else torch.as_tensor(env_ids, device=dev).long()
+        s = self._env.state
+        f32 = lambda t: None if t is None else torch.as_tensor(t, dtype=torch.float32, device=dev)  # noqa: E731
+        off_pos, off_quat = world_pose_offsets(s["root_pos"][:, ids].T, s["root_quat"][:, ids].T, f32(positions),
+                                               f32(orientations), convention)
+        if off_pos is not None:
+            self.offset[:3, ids] = off_pos.T
+        if off_quat is not None:
+            self.offset[3:, ids] = off_quat.T
+        self._dirty = True
+
+    def set_world_poses_from_view(self, eyes, targets, env_ids=None) -> None:
+        raise NotImplementedError("camera.set_world_poses_from_view is not served: build the orientation and call "
+                                  "set_world_poses")
+
+
 class _ImuData:
     """``ImuData`` (imu_data.py) of one sensor: zero-copy strided views of the env-minor device buffer, as the last
     launch left them.  Positions are env-local, like every other view here (envs/scene.py)."""

@@ -421,6 +421,41 @@ typedef struct {
 int as_imu(as_env_t* env, const as_imu_table_t* host, float dt, int all, uint8_t* outdated, float* data, float* prev,
            void* stream);
 
+/* The reference's RayCasterCamera sensor (ray_caster_camera.py:257-318; a depth camera with a pinhole pattern) over
+ * the ground plane and the env's stones, off by default: one launch of k_ray_camera on `stream` over the state as it
+ * stands, never part of as_step.  One added symbol and one added struct: AS_ABI_VERSION stays 6.  R = width * height:
+ *   dirs    [3][R]      device memory: the local direction of every pixel, row-major over the image (pixel (row v,
+ *                       column u) is ray v * width + u), camera frame in the "world" convention (x forward, z up)
+ *   offset  [7][n]      device memory: the camera frame in the root link's frame, position | quaternion (w, x, y, z)
+ *                       in the "world" convention, used as given (not normalised)
+ *   pose    [7][n]      out: the camera's pos_w | quat_w_world
+ *   plane   [n][R]      out, may be NULL: distance_to_image_plane, the hit's x coordinate in the camera frame
+ *   camera  [n][R]      out, may be NULL: distance_to_camera, the distance along the ray in units of |direction|
+ *   normals [n][R][3]   out, may be NULL: the outward unit normal of the face hit
+ * The images are env-major and contiguous: (n, height, width, 1 | 3).  Every ray starts at the camera's position.
+ * surfaces selects what is cast against, as in as_ray_cast, with the same tie rules; the cast's own distance cap is
+ * 1e6.  A miss: camera = +inf, plane = NaN (inf times the direction, rotated), normals = +inf.  clipping then maps
+ * values above max_distance -- and, in plane, NaN -- to max_distance (AS_CAM_CLIP_MAX) or 0 (AS_CAM_CLIP_ZERO);
+ * normals are never clipped (csrc/allsteps_ray_camera.h has the formulas and the float32 rounding order).
+ * AS_ERR_INVALID, before any device call, for a NULL env / cfg / dirs / offset / pose, all three images NULL, a
+ * non-positive width or height or width * height above AS_MAX_CAMERA_RAYS, surfaces 0 or with unknown bits, an
+ * unknown clipping, a max_distance that is not finite or <= 0, a ground_z that is not finite.  Graph-safe: dirs and
+ * offset are read from device memory at every launch. */
+#define AS_MAX_CAMERA_RAYS 16384 /* 128 x 128 */
+#define AS_CAM_CLIP_NONE 0
+#define AS_CAM_CLIP_MAX 1
+#define AS_CAM_CLIP_ZERO 2
+typedef struct {
+  int32_t width;
+  int32_t height;
+  int32_t surfaces;     /* AS_RAY_GROUND | AS_RAY_STONES */
+  int32_t clipping;     /* AS_CAM_CLIP_* */
+  float max_distance;
+  float ground_z;
+} as_ray_camera_t;
+int as_ray_camera(as_env_t* env, const as_ray_camera_t* cfg_host, const float* dirs, const float* offset,
+                  float* pose, float* plane, float* camera, float* normals, void* stream);
+
 /* Noise models, off by default: DirectRLEnv.step's cfg.action_noise_model / cfg.observation_noise_model
  * (direct_rl_env.py:322-323, 379-380, 578-581; isaaclab/utils/noise/noise_model.py).  Stateless entry points
  * over caller-owned device buffers -- no as_env_t: the env step itself is unchanged, the caller launches
