@@ -28,6 +28,7 @@ EXPORTED_SYMBOLS = [
     "as_build_id", "as_step_counters_host", "as_body_state", "as_sweep_plan", "as_set_contact_report",
     "as_contact_forces", "as_noise_actions", "as_noise_post", "as_events_init", "as_events_interval",
     "as_contact_timers", "as_ray_cast", "as_imu", "as_ray_camera",
+    "as_frame_transformer",
 ]
 MAXB = 32  # AS_MAX_BODIES
 MAXC = 10  # AS_MAX_CONTACTS
@@ -43,6 +44,10 @@ CAM_CLIP_NONE, CAM_CLIP_MAX, CAM_CLIP_ZERO = 0, 1, 2  # AS_CAM_CLIP_* (as_ray_ca
 MAX_IMUS = 8  # AS_MAX_IMUS
 IMU_DATA_ROWS = 19  # as_imu data rows: pos 3 | quat 4 | lin_vel_b 3 | ang_vel_b 3 | lin_acc_b 3 | ang_acc_b 3
 IMU_PREV_ROWS = 6  # as_imu prev rows: world linear | angular velocity of the previous update
+MAX_FRAME_TRANSFORMERS = 4  # AS_MAX_FRAME_TRANSFORMERS
+MAX_FRAMES = 32  # AS_MAX_FRAMES
+FRAME_SOURCE_ROWS = 7  # as_frame_transformer source rows: pos 3 | quat 4
+FRAME_TARGET_ROWS = 14  # as_frame_transformer target rows: pos_w 3 | quat_w 4 | pos_source 3 | quat_source 4
 BODY_STATE_ROWS = 16  # AS_BODY_STATE_ROWS: pos 3 | quat 4 | frame lin vel 3 | ang vel 3 | COM lin vel 3
 
 
@@ -74,6 +79,21 @@ class AsImuTable(C.Structure):
                 ("body_offset_pos", (C.c_float * 3) * MAX_IMUS), ("body_offset_quat", (C.c_float * 4) * MAX_IMUS),
                 ("com", (C.c_float * 3) * MAX_IMUS), ("offset_pos", (C.c_float * 3) * MAX_IMUS),
                 ("offset_rot", (C.c_float * 4) * MAX_IMUS), ("gravity_bias", (C.c_float * 3) * MAX_IMUS)]
+
+
+class AsFrameBody(C.Structure):
+    """as_frame_body_t (include/allsteps.h): the body (link >= 0) or stone (link < 0) a frame sits on, and its offset."""
+    _fields_ = [("link", C.c_int32), ("stone", C.c_int32), ("body_offset_pos", C.c_float * 3),
+                ("body_offset_quat", C.c_float * 4), ("offset_pos", C.c_float * 3), ("offset_rot", C.c_float * 4)]
+
+
+class AsFrameTable(C.Structure):
+    """as_frame_table_t (include/allsteps.h): the sensors and target frames of one as_frame_transformer call."""
+    _fields_ = [("num_sensors", C.c_int32), ("num_frames", C.c_int32),
+                ("apply_source_offset", C.c_int32 * MAX_FRAME_TRANSFORMERS),
+                ("apply_target_offset", C.c_int32 * MAX_FRAME_TRANSFORMERS),
+                ("source", AsFrameBody * MAX_FRAME_TRANSFORMERS), ("target", AsFrameBody * MAX_FRAMES),
+                ("sensor", C.c_int32 * MAX_FRAMES)]
 
 
 class AsContactReport(C.Structure):
@@ -315,6 +335,7 @@ def load() -> C.CDLL:
     L.as_contact_timers.argtypes = [V, V, V, V, C.c_float, I32, V, V, V]
     L.as_ray_cast.argtypes = [V, V, V, V, V, V, V]
     L.as_imu.argtypes = [V, V, C.c_float, I32, V, V, V, V]
+    L.as_frame_transformer.argtypes = [V, V, V, V, V]
     L.as_ray_camera.argtypes = [V, V, V, V, V, V, V, V, V]
     L.as_noise_actions.argtypes = [V, V, V, I32, I32, V, V, U64, I64, V]
     L.as_noise_post.argtypes = [V, V, V, I32, I32, V, V, V, V, V, V, U64, I64, V]
@@ -568,6 +589,12 @@ class NativeEnv:
         every env), flags cleared; data fp32 [IMU_DATA_ROWS][S][n], prev fp32 [IMU_PREV_ROWS][S][n]."""
         check(self.L.as_imu(self.h, C.byref(table) if table is not None else None, dt, int(bool(all_envs)),
                             _ptr(outdated), _ptr(data), _ptr(prev), stream), "as_imu")
+
+    def frame_transformer(self, table: "AsFrameTable", source, target, stream=None):
+        """as_frame_transformer: every target frame of every sensor of `table` from the state as it stands; source
+        fp32 [FRAME_SOURCE_ROWS][S][n], target fp32 [FRAME_TARGET_ROWS][F][n]."""
+        check(self.L.as_frame_transformer(self.h, C.byref(table) if table is not None else None, _ptr(source),
+                                          _ptr(target), stream), "as_frame_transformer")
 
     def set_actuator(self, mode: int, action_scale: float = 0.0, default_q=(), stiffness: float = 0.0,
                      damping: float = 0.0, saturation_effort: float = 0.0, effort_limit: float = 0.0,

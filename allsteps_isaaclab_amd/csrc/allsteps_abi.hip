@@ -687,6 +687,52 @@ int as_imu(as_env_t* env, const as_imu_table_t* host, float dt, int all, uint8_t
   return AS_OK;
 }
 
+int as_frame_transformer(as_env_t* env, const as_frame_table_t* host, float* source, float* target, void* stream) {
+  // (what needs no handle is checked first, the handle and what it sizes after)
+  if (!host) return fail(AS_ERR_INVALID, "as_frame_transformer: null argument host");
+  if (!source) return fail(AS_ERR_INVALID, "as_frame_transformer: null argument source");
+  if (!target) return fail(AS_ERR_INVALID, "as_frame_transformer: null argument target");
+  const as_frame_table_t& t = *host;
+  const int S = t.num_sensors, F = t.num_frames;
+  if (S < 1 || S > AS_MAX_FRAME_TRANSFORMERS)
+    return fail(AS_ERR_INVALID, "as_frame_transformer: num_sensors " + std::to_string(S) +
+                                    " outside [1, AS_MAX_FRAME_TRANSFORMERS = " +
+                                    std::to_string(AS_MAX_FRAME_TRANSFORMERS) + "]");
+  if (F < 1 || F > AS_MAX_FRAMES)
+    return fail(AS_ERR_INVALID, "as_frame_transformer: num_frames " + std::to_string(F) +
+                                    " outside [1, AS_MAX_FRAMES = " + std::to_string(AS_MAX_FRAMES) + "]");
+  for (int f = 0; f < F; ++f) {
+    const int s = t.sensor[f], before = f ? t.sensor[f - 1] : 0;
+    if (s < 0 || s >= S)
+      return fail(AS_ERR_INVALID, "as_frame_transformer: frame " + std::to_string(f) + " sensor " + std::to_string(s) +
+                                      " outside [0, " + std::to_string(S) + ")");
+    if ((f == 0 && s != 0) || s < before || s > before + 1 || (f == F - 1 && s != S - 1))
+      return fail(AS_ERR_INVALID, "as_frame_transformer: frame " + std::to_string(f) + " sensor " + std::to_string(s) +
+                                      " out of order: frames are grouped by sensor, every sensor has one");
+  }
+  if (!env) return fail(AS_ERR_INVALID, "as_frame_transformer: null argument env");
+  const int links = env->host.model.num_links, stones = env->host.task.num_steps;
+  for (int i = 0; i < S + F; ++i) {
+    const as_frame_body_t& b = i < S ? t.source[i] : t.target[i - S];
+    const std::string what = i < S ? "sensor " + std::to_string(i) + " source" : "frame " + std::to_string(i - S);
+    if (b.link >= links)
+      return fail(AS_ERR_INVALID, "as_frame_transformer: " + what + " link " + std::to_string(b.link) +
+                                      " outside the model's " + std::to_string(links) + " links");
+    if (b.link < 0 && (b.stone < 0 || b.stone >= stones))
+      return fail(AS_ERR_INVALID, "as_frame_transformer: " + what + " stone " + std::to_string(b.stone) +
+                                      " outside [0, num_steps = " + std::to_string(stones) + ")");
+  }
+  as::FrameTransformerArgs a{};
+  a.consts = env->consts_dev;
+  a.st = env->st;
+  a.n = env->n;
+  a.source = source;
+  a.target = target;
+  a.frames = t;
+  HIP_TRY(as::launch_frame_transformer(a, reinterpret_cast<hipStream_t>(stream)));
+  return AS_OK;
+}
+
 // as_noise_*: a model's ranges and pointers.  `what` names the call and the model in the message.
 static bool noise_model_ok(const as_noise_model_t& m, const std::string& what, std::string& err) {
   if (m.kind < AS_NOISE_CONSTANT || m.kind > AS_NOISE_GAUSSIAN)

@@ -158,6 +158,18 @@ struct ImuArgs {
   as_imu_table_t imus;
 };
 
+// k_frame_transformer (as_frame_transformer, frame_transformer_kernels.h): k_body_state's FK, then every target
+// frame of every sensor in the world and in its source frame; buffers field-major / env-minor
+// (allsteps_frame_transformer.h)
+struct FrameTransformerArgs {
+  const Consts* consts;
+  as_state_t st;
+  int32_t n;
+  float* source;               // [7][S][n]
+  float* target;               // [14][F][n]
+  as_frame_table_t frames;
+};
+
 // k_contact_forces (as_contact_forces): dense sums over the contact report
 struct ForcesArgs {
   int32_t n;
@@ -277,6 +289,7 @@ bool step_supported_nv(int nv);
 hipError_t launch_ray_cast(RayArgs a, hipStream_t stream);
 hipError_t launch_ray_camera(const CamArgs& a, hipStream_t stream);
 hipError_t launch_imu(const ImuArgs& a, hipStream_t stream);
+hipError_t launch_frame_transformer(const FrameTransformerArgs& a, hipStream_t stream);
 hipError_t launch_contact_timers(const TimersArgs& a, hipStream_t stream);
 hipError_t launch_events_interval(const EventsArgs& a, hipStream_t stream);
 hipError_t launch_events_init(const EventsArgs& a, hipStream_t stream);

@@ -26,8 +26,8 @@
 //   contact report's stores -> step_task.h  task helpers;
 // after k_step: task_kernels.h (k_obs, k_stones, k_quad), body_state_kernel.h (k_body_state) and
 // contact_forces_kernel.h (k_contact_forces), noise_kernels.h, event_kernels.h, contact_timer_kernels.h
-// (k_contact_timers), ray_caster_kernels.h (k_ray_cast), imu_kernels.h (k_imu) and ray_camera_kernels.h
-// (k_ray_camera).
+// (k_contact_timers), ray_caster_kernels.h (k_ray_cast), imu_kernels.h (k_imu), ray_camera_kernels.h
+// (k_ray_camera) and frame_transformer_kernels.h (k_frame_transformer).
 #include <hip/hip_runtime.h>
 
 #include "../../include/allsteps.h"
@@ -464,6 +464,7 @@ __global__ __launch_bounds__(kStepThreads) __attribute__((amdgpu_waves_per_eu(2,
 #include "contact_timer_kernels.h"
 #include "ray_caster_kernels.h"
 #include "imu_kernels.h"
+#include "frame_transformer_kernels.h"
 #include "ray_camera_kernels.h"
 
 namespace as {
@@ -559,6 +560,12 @@ hipError_t launch_contact_timers(const TimersArgs& a, hipStream_t stream) {
 hipError_t launch_imu(const ImuArgs& a, hipStream_t stream) {
   const int blocks = (a.n + EPB - 1) / EPB;
   hipLaunchKernelGGL(k_imu, dim3(blocks), dim3(kStepThreads), 0, stream, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_frame_transformer(const FrameTransformerArgs& a, hipStream_t stream) {
+  const int blocks = (a.n + EPB - 1) / EPB;
+  hipLaunchKernelGGL(k_frame_transformer, dim3(blocks), dim3(kStepThreads), 0, stream, a);
   return hipGetLastError();
 }
 

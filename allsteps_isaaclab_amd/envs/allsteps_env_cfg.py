@@ -93,6 +93,13 @@ class AllstepsEnvCfg:
     # are outdated -- all of them after a step or a reset, the envs of a masked reset -- whenever a sensor's data is
     # read.  The step, its observation and the state are as ever either way.  None: nothing allocated or launched.
     imu: object = None
+    # Frame transformers over the robot's bodies and the env's stones (the reference's FrameTransformerCfg): a
+    # utils.sensors.FrameTransformerCfg -- then env.frame_transformer and env.scene.sensors["frame_transformer"] --
+    # or a dict of name -> FrameTransformerCfg (at most 4, 32 target frames in all), or None.  One HIP kernel
+    # (csrc/frame_transformer_kernels.h) forms every target frame in the world and in its source frame whenever a
+    # sensor's data is read after the scene changed.  The step, its observation and the state are as ever either
+    # way.  None: nothing allocated or launched.
+    frame_transformer: object = None
     # ray-cast depth cameras on the root body (the reference's RayCasterCameraCfg): a utils.sensors.RayCasterCameraCfg
     # -- then env.camera and env.scene.sensors["camera"] -- or a dict of name -> cfg (at most 4), or None.  One HIP
     # kernel (csrc/ray_camera_kernels.h) casts a camera's pixels against the ground and the stones whenever its data

@@ -91,6 +91,9 @@ class AnymalCStonesEnvCfg:
     height_scanner: object = None
     # IMU sensors on the robot's bodies (as AllstepsEnvCfg.imu): a utils.sensors.ImuCfg, a dict of them, or None
     imu: object = None
+    # frame transformers over the robot's bodies and the stones (as AllstepsEnvCfg.frame_transformer): a
+    # utils.sensors.FrameTransformerCfg, a dict of them, or None
+    frame_transformer: object = None
     # ray-cast depth cameras on the root body (the reference's RayCasterCameraCfg): a utils.sensors.RayCasterCameraCfg
     # -- then env.camera and env.scene.sensors["camera"] -- or a dict of name -> cfg (at most 4), or None.  One HIP
     # kernel (csrc/ray_camera_kernels.h) casts a camera's pixels against the ground and the stones whenever its data

@@ -9,12 +9,13 @@ import torch
 from .. import _native
 from .direct_rl_env import DirectRLEnv
 from .state import alloc_state
-from .views import _ContactReport, _ContactTimers, _ImuSet, _RayCaster, _RayCasterCamera
+from .views import _ContactReport, _ContactTimers, _FrameTransformerSet, _ImuSet, _RayCaster, _RayCasterCamera
 
 
 class NativeDirectEnv(DirectRLEnv):
     _native = None  # the NativeEnv handle: None before _init_native and after close
     _contact_timers = None  # the _ContactTimers of cfg.contact_air_time, or None: nothing allocated or launched
+    _frame_transformers = None  # the _FrameTransformerSet of cfg.frame_transformer, or None: the same
 
     def _init_native(self, model: dict, *, hind: bool = False, feet: bool = False, env_id_offset: int = 0,
                      contact_forces: bool | None = None) -> None:
@@ -25,7 +26,8 @@ class NativeDirectEnv(DirectRLEnv):
         With ``cfg.height_scanner`` it also builds the ray-caster sensor (``env.height_scanner``,
         ``env.scene.sensors["height_scanner"]``), with ``cfg.camera`` the ray-cast cameras (``env.scene.sensors[name]``;
         ``env.camera`` for a single cfg), with ``cfg.imu`` the IMUs (``env.scene.sensors[name]``; ``env.imu``
-        for a single cfg).  Env-specific initial values are the caller's."""
+        for a single cfg), with ``cfg.frame_transformer`` the frame transformers (``env.scene.sensors[name]``;
+        ``env.frame_transformer`` for a single cfg).  Env-specific initial values are the caller's."""
         dev = self._device
         if dev.type != "cuda" or not torch.cuda.is_available():
             raise _native.NativeError(f"{type(self).__name__} runs on the HIP backend only (device={dev}, HIP device "
@@ -71,6 +73,17 @@ class NativeDirectEnv(DirectRLEnv):
                 self.scene.sensors.update(self._imus.sensors)
                 if not isinstance(imu, dict):
                     self.imu = self._imus.sensors["imu"]
+            ft = getattr(self.cfg, "frame_transformer", None)
+            if ft is not None:  # lazy like the height scanner; one launch serves them all
+                self._frame_transformers = _FrameTransformerSet(self, ft)
+                taken = sorted(set(self._frame_transformers.sensors) & set(self.scene.sensors))
+                if taken:
+                    raise _native.NativeError(f"cfg.frame_transformer: the sensor names {taken} are already registered "
+                                              f"in the scene")
+                self.scene.sensors.update(self._frame_transformers.sensors)
+                self._add_lazy_sensor(self._frame_transformers)
+                if not isinstance(ft, dict):
+                    self.frame_transformer = self._frame_transformers.sensors["frame_transformer"]
             self._events_start()
 
     episode_length_buf = property(lambda self: self.state["ep_len"])

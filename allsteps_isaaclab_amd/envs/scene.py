@@ -34,7 +34,7 @@ def grid_env_origins(num_envs: int, env_spacing: float, device="cpu") -> torch.T
 class SceneView:
     """``env.scene``: ``num_envs``, ``cfg``, ``env_origins`` (the plane terrain's grid) and ``sensors`` -- the
     sensors an env registers by name (``height_scanner`` with cfg.height_scanner, the cameras of cfg.camera, the IMUs
-    of cfg.imu); empty otherwise.  ``scene[name]`` is the reference's lookup of a scene entity: here, a sensor."""
+    of cfg.imu, the frame transformers of cfg.frame_transformer); empty otherwise.  ``scene[name]`` is the reference's lookup of a scene entity: here, a sensor."""
 
     def __init__(self, cfg, device):
         self.cfg = cfg

@@ -697,6 +697,103 @@ class _ImuSet:
         self.mark_all()
 
 
+class _FrameTransformerData:
+    """``FrameTransformerData`` (frame_transformer_data.py) of one sensor: zero-copy strided views of the env-minor
+    device buffers, as the last launch left them.  Positions are env-local, like every other view here
+    (envs/scene.py); the poses in the source frame do not depend on that."""
+
+    def __init__(self, group: "_FrameTransformerSet", s: int, frames: slice, names: list):
+        self._g, self._i, self._f = group, s, frames
+        self.target_frame_names = names  # the order of envs/frame_transformer.py
+
+    source_pos_w = property(lambda self: self._g.source[0:3, self._i].T)  # (N, 3)
+    source_quat_w = property(lambda self: self._g.source[3:7, self._i].T)  # (N, 4) (w, x, y, z)
+    target_pos_w = property(lambda self: self._g.target[0:3, self._f].permute(2, 1, 0))  # (N, F_s, 3)
+    target_quat_w = property(lambda self: self._g.target[3:7, self._f].permute(2, 1, 0))  # (N, F_s, 4)
+    target_pos_source = property(lambda self: self._g.target[7:10, self._f].permute(2, 1, 0))
+    target_quat_source = property(lambda self: self._g.target[10:14, self._f].permute(2, 1, 0))
+
+
+class _FrameTransformer:
+    """One frame transformer of an env (the reference's ``FrameTransformer``, frame_transformer.py): sensor
+    ``index`` of the env's ``_FrameTransformerSet``, which owns the buffers and the launch."""
+
+    def __init__(self, group: "_FrameTransformerSet", index: int, name: str, cfg):
+        self._g, self.index, self.name, self.cfg = group, index, name, cfg
+        spec = group._spec
+        self._data = _FrameTransformerData(group, index, spec.slices[index], list(spec.frame_names[index]))
+        self._source_body = spec.sources[index][2]
+        self._target_bodies = list(dict.fromkeys(body[2] for body, _, _ in spec.frames[index]))
+
+    def __str__(self) -> str:
+        names = self._data.target_frame_names
+        return (f"FrameTransformer @ '{self.cfg.prim_path}': \n"
+                f"\ttracked body frames: {[self._source_body] + self._target_bodies} \n"
+                f"\tnumber of envs: {self.num_instances}\n"
+                f"\tsource body frame: {self._source_body}\n"
+                f"\ttarget frames (count: {names}): {len(names)}\n")
+
+    num_instances = property(lambda self: self._g._env.num_envs)
+    device = property(lambda self: self._g._env.device)
+    launches = property(lambda self: self._g.launches)  # as_frame_transformer launches so far (one serves all)
+
+    @property
+    def data(self) -> _FrameTransformerData:
+        """The sensor's buffers, after one launch if the scene changed since the last one; a second read launches
+        nothing."""
+        self._g.refresh()
+        return self._data
+
+    def update(self, dt: float = 0.0, force_recompute: bool = False) -> None:
+        """SensorBase.update: with ``force_recompute`` one launch now, on the env's current stream -- the call to
+        put inside a captured graph; otherwise the next read of ``data`` decides."""
+        if force_recompute:
+            self._g._launch()
+
+    def reset(self, env_ids=None) -> None:
+        """SensorBase.reset: nothing is kept per env but the outdated flag, which here is the set's."""
+        self._g.mark_dirty()
+
+
+class _FrameTransformerSet:
+    """The frame transformers of an env (``cfg.frame_transformer``): the device buffers of ``as_frame_transformer``
+    (csrc/allsteps_frame_transformer.h) and the one launch that serves every sensor.  Lazy like the height scanner:
+    a read of any sensor's ``data`` launches only when the env has marked the scene changed since the last launch
+    (``mark_dirty``: step, graph-replay accounting, every reset path, set_state, the robot view's writers, stone
+    regeneration); ``update(dt, force_recompute=True)`` always launches.  The sensors keep nothing between updates:
+    recomputing an env that the reference would have left alone gives the same bits from the same state, so there is
+    no per-env outdated buffer, and there are no get_state keys."""
+
+    def __init__(self, env, cfg):
+        from .frame_transformer import FrameTransformerSpec
+
+        n, dev = env.num_envs, env._device
+        spec = FrameTransformerSpec(cfg, model=env.model, num_steps=int(env.cfg.num_steps), step_dt=env.step_dt)
+        self._env, self._spec = env, spec
+        self._table = spec.table()
+        self.num_sensors, self.num_frames = spec.num_sensors, spec.num_frames
+        # zeros before the first update, as the reference's buffers (frame_transformer.py:315-320)
+        self.source = torch.zeros(_native.FRAME_SOURCE_ROWS, self.num_sensors, n, dtype=torch.float32, device=dev)
+        self.target = torch.zeros(_native.FRAME_TARGET_ROWS, self.num_frames, n, dtype=torch.float32, device=dev)
+        self._dirty = True
+        self.launches = 0
+        self.sensors = {name: _FrameTransformer(self, s, name, c)
+                        for s, (name, c) in enumerate(zip(spec.names, spec.cfgs))}
+
+    def mark_dirty(self) -> None:
+        self._dirty = True
+
+    def _launch(self) -> None:
+        env = self._env
+        env._native.frame_transformer(self._table, self.source, self.target, stream=env._stream())
+        self.launches += 1
+        self._dirty = False
+
+    def refresh(self) -> None:
+        if self._dirty:
+            self._launch()
+
+
 class _RobotView:
     """Minimal ``Articulation`` surface: ``data`` plus the state writers used on reset (each tells the env that the
     scene changed: a lazy sensor recomputes on its next read)."""

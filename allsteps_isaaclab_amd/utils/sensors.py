@@ -1,12 +1,13 @@
-"""Sensor configuration -- ``RayCasterCfg``, ``RayCasterCameraCfg``, ``patterns`` and ``ImuCfg`` of
-``isaaclab.sensors`` and the observation functions ``height_scan``, ``image``, ``imu_orientation``, ``imu_ang_vel``
-and ``imu_lin_acc`` of ``isaaclab.envs.mdp``, same names, fields and defaults, for ``cfg.height_scanner``,
-``cfg.camera`` and ``cfg.imu`` of the envs.
+"""Sensor configuration -- ``RayCasterCfg``, ``RayCasterCameraCfg``, ``patterns``, ``ImuCfg``,
+``FrameTransformerCfg`` and ``OffsetCfg`` of ``isaaclab.sensors`` and the observation functions ``height_scan``,
+``image``, ``imu_orientation``, ``imu_ang_vel`` and ``imu_lin_acc`` of ``isaaclab.envs.mdp``, same names, fields and
+defaults, for ``cfg.height_scanner``, ``cfg.camera``, ``cfg.imu`` and ``cfg.frame_transformer`` of the envs.
 
 The rays are cast on the device (``k_ray_cast``, csrc/ray_caster_kernels.h; the camera's by ``k_ray_camera``,
 csrc/ray_camera_kernels.h) against the ground plane and the env's stones, and the IMUs are updated on the device
-(``k_imu``, csrc/imu_kernels.h); the env raises at construction for what those kernels do not serve
-(envs/ray_caster.py, envs/ray_camera.py, envs/imu.py).
+(``k_imu``, csrc/imu_kernels.h), as are the frame transformers (``k_frame_transformer``,
+csrc/frame_transformer_kernels.h); the env raises at construction for what those kernels do not serve
+(envs/ray_caster.py, envs/ray_camera.py, envs/imu.py, envs/frame_transformer.py).
 """
 
 from __future__ import annotations
@@ -122,3 +123,34 @@ def imu_ang_vel(env, asset_cfg: SceneEntityCfg = SceneEntityCfg("imu")):
 def imu_lin_acc(env, asset_cfg: SceneEntityCfg = SceneEntityCfg("imu")):
     """observations.py ``imu_lin_acc``: the linear acceleration (m/s^2) in the sensor frame -- (N, 3)."""
     return env.scene[asset_cfg.name].data.lin_acc_b
+
+
+@dataclass
+class OffsetCfg:
+    """frame_transformer_cfg.py ``OffsetCfg``: the offset pose of one frame relative to another frame."""
+
+    pos: tuple = (0.0, 0.0, 0.0)
+    rot: tuple = (1.0, 0.0, 0.0, 0.0)  # (w, x, y, z)
+
+
+@dataclass
+class FrameTransformerCfg:
+    """frame_transformer_cfg.py ``FrameTransformerCfg`` with ``SensorBaseCfg``'s fields (sensor_base_cfg.py);
+    ``visualizer_cfg`` serves ``debug_vis`` only, which a headless env refuses."""
+
+    @dataclass
+    class FrameCfg:
+        """Information specific to a coordinate frame: the body (a regex may match several), the frame's name
+        (None: the body's) and its pose in the body's frame."""
+
+        prim_path: str = MISSING
+        name: Any = None  # str | None
+        offset: OffsetCfg = field(default_factory=OffsetCfg)
+
+    prim_path: str = MISSING
+    update_period: float = 0.0
+    history_length: int = 0
+    debug_vis: bool = False
+    source_frame_offset: OffsetCfg = field(default_factory=OffsetCfg)
+    target_frames: Any = MISSING  # list[FrameCfg]
+    visualizer_cfg: Any = None

@@ -421,6 +421,46 @@ typedef struct {
 int as_imu(as_env_t* env, const as_imu_table_t* host, float dt, int all, uint8_t* outdated, float* data, float* prev,
            void* stream);
 
+/* The reference's FrameTransformer sensor (frame_transformer.py:322-385) over the model's bodies and the env's
+ * stones, off by default: one launch of k_frame_transformer on `stream` over the state as it stands, never part of
+ * as_step.  One added symbol and two added structs: AS_ABI_VERSION stays 6.  The launch runs as_body_state's FK and
+ * forms, for each of the F = num_frames target frames of the S = num_sensors sensors, the frame's pose in the world
+ * and in its sensor's source frame (csrc/allsteps_frame_transformer.h has the formulas and the float32 rounding
+ * order):
+ *   source [7][S][n]    out: the source frame's pos 3 | quat 4 (w, x, y, z)
+ *   target [14][F][n]   out: pos_w 3 | quat_w 4 | pos_source 3 | quat_source 4
+ * A frame sits on a robot body (link >= 0: link / body_offset_* are the as_body_table_t row of the body; its link
+ * pose is as_body_state rows 0:7) or on a stone (link < 0: position state.stones rows 3 stone .. 3 stone + 2,
+ * quaternion (1, 0, 0, 0)), moved by offset_pos / offset_rot (offset_rot is used as given) where the sensor's switch
+ * says so: apply_source_offset for the source, apply_target_offset for EVERY target frame of the sensor, identity
+ * offsets included (the reference's two switches; a product with the identity quaternion is not a no-op in float32).
+ * Frames are grouped by sensor: sensor[] starts at 0, never decreases, steps by at most 1 and ends at S - 1.
+ * Positions are env-local.  The sensor keeps no state: the buffers are a function of the state as it stands.
+ * AS_ERR_INVALID, before any device call, for a NULL env / table / source / target, num_sensors outside
+ * [1, AS_MAX_FRAME_TRANSFORMERS], num_frames outside [1, AS_MAX_FRAMES], a link outside the model, a stone outside
+ * [0, task.num_steps), a frame whose sensor is outside [0, S) or out of order.  Graph-safe: the table is captured
+ * by value. */
+#define AS_MAX_FRAME_TRANSFORMERS 4
+#define AS_MAX_FRAMES 32
+typedef struct {
+  int32_t link;             /* >= 0: the link whose frame carries the body; < 0: the frame sits on a stone */
+  int32_t stone;            /* the stone (link < 0) */
+  float body_offset_pos[3]; /* the body frame in that link's frame (as_body_table_t.offset_pos) */
+  float body_offset_quat[4];/* (w, x, y, z) */
+  float offset_pos[3];      /* the frame in the body's (the stone's) frame (OffsetCfg.pos) */
+  float offset_rot[4];      /* (w, x, y, z), not normalised (OffsetCfg.rot) */
+} as_frame_body_t;
+typedef struct {
+  int32_t num_sensors;
+  int32_t num_frames;
+  int32_t apply_source_offset[AS_MAX_FRAME_TRANSFORMERS]; /* != 0: the source offset is applied */
+  int32_t apply_target_offset[AS_MAX_FRAME_TRANSFORMERS]; /* != 0: every target offset of the sensor is applied */
+  as_frame_body_t source[AS_MAX_FRAME_TRANSFORMERS];      /* per sensor: the source body and the source offset */
+  as_frame_body_t target[AS_MAX_FRAMES];                  /* per frame: the target body and the frame's offset */
+  int32_t sensor[AS_MAX_FRAMES];                          /* per frame: the sensor it belongs to */
+} as_frame_table_t;
+int as_frame_transformer(as_env_t* env, const as_frame_table_t* host, float* source, float* target, void* stream);
+
 /* The reference's RayCasterCamera sensor (ray_caster_camera.py:257-318; a depth camera with a pinhole pattern) over
  * the ground plane and the env's stones, off by default: one launch of k_ray_camera on `stream` over the state as it
  * stands, never part of as_step.  One added symbol and one added struct: AS_ABI_VERSION stays 6.  R = width * height:
