@@ -28,7 +28,7 @@ EXPORTED_SYMBOLS = [
     "as_build_id", "as_step_counters_host", "as_body_state", "as_sweep_plan", "as_set_contact_report",
     "as_contact_forces", "as_noise_actions", "as_noise_post", "as_events_init", "as_events_interval",
     "as_contact_timers", "as_ray_cast", "as_imu", "as_ray_camera",
-    "as_frame_transformer",
+    "as_frame_transformer", "as_commands_step", "as_commands_reset",
 ]
 MAXB = 32  # AS_MAX_BODIES
 MAXC = 10  # AS_MAX_CONTACTS
@@ -163,6 +163,45 @@ def events_interval(terms, root_lin, root_ang, time_left, t, dt: float, fired=No
                                     time_left.data_ptr(), t.data_ptr(), _ptr(fired), n, dt, _ptr(interval_draws),
                                     _ptr(push_draws), seed & 0xFFFFFFFFFFFFFFFF, env_offset, stream),
           "as_events_interval")
+
+
+MAX_COMMAND_TERMS = 4  # AS_MAX_COMMAND_TERMS
+COMMAND_DRAWS = 11  # AS_COMMAND_DRAWS: draws a term consumes per resample at most
+COMMAND_UNIFORM, COMMAND_NORMAL = 0, 1  # AS_COMMAND_UNIFORM / AS_COMMAND_NORMAL
+COMMAND_FLAG_ROWS = 5  # is_heading, is_standing, is_zero_vel_x / y / yaw
+COMMAND_METRIC_ROWS = 2  # error_vel_xy, error_vel_yaw
+# as_command_term_t as 21 32-bit words: kind, heading (int32) | time_lo, time_w | lo[4] | w[4] | clip_lo, clip_hi |
+# stiffness | p_heading | p_standing | p_zero[3] | max_command_step (float32)
+COMMAND_TERM_WORDS = 21
+# Philox tags of the command streams (csrc/allsteps_commands.h): the reset's resample, the compute's
+COMMAND_TAGS = (0x436D5273, 0x436D4370)
+
+
+def commands_step(terms, root_quat, root_lin, root_ang, vel, heading_target, flags, time_left, counter, metrics,
+                  last_metrics, t, dt: float, reset=None, reset2=None, draws=None, seed: int = 0, env_offset: int = 0,
+                  stream=None):
+    """as_commands_step: the reset of the envs in reset | reset2 ((n,) uint8 / bool, None: none), then
+    CommandTerm.compute(dt) of every env, every term.  terms: (terms, 21) float32 device rows of as_command_term_t;
+    root_quat (4, n), root_lin / root_ang (3, n); vel (terms, 3, n), heading_target (terms, n), flags (terms, 5, n)
+    uint8, time_left (terms, n), counter (terms, n) int32, metrics / last_metrics (terms, 2, n) (last_metrics may
+    be None), t (n,); draws (2, terms, 11, n) injected or None (Philox)."""
+    k, n = time_left.shape
+    check(load().as_commands_step(terms.data_ptr(), k, root_quat.data_ptr(), root_lin.data_ptr(),
+                                  root_ang.data_ptr(), vel.data_ptr(), heading_target.data_ptr(), flags.data_ptr(),
+                                  time_left.data_ptr(), counter.data_ptr(), metrics.data_ptr(), _ptr(last_metrics),
+                                  t.data_ptr(), _ptr(reset), _ptr(reset2), n, dt, _ptr(draws),
+                                  seed & 0xFFFFFFFFFFFFFFFF, env_offset, stream), "as_commands_step")
+
+
+def commands_reset(terms, vel, heading_target, flags, time_left, counter, metrics, last_metrics, t, mask=None,
+                   draws=None, seed: int = 0, env_offset: int = 0, stream=None):
+    """as_commands_reset: CommandTerm.reset of the envs in mask ((n,) uint8 / bool, None: all), no compute; draws
+    (terms, 11, n) injected or None (Philox)."""
+    k, n = time_left.shape
+    check(load().as_commands_reset(terms.data_ptr(), k, vel.data_ptr(), heading_target.data_ptr(), flags.data_ptr(),
+                                   time_left.data_ptr(), counter.data_ptr(), metrics.data_ptr(), _ptr(last_metrics),
+                                   t.data_ptr(), _ptr(mask), n, _ptr(draws), seed & 0xFFFFFFFFFFFFFFFF, env_offset,
+                                   stream), "as_commands_reset")
 
 
 def unpack_report_ids(w):
@@ -341,6 +380,8 @@ def load() -> C.CDLL:
     L.as_noise_post.argtypes = [V, V, V, I32, I32, V, V, V, V, V, V, U64, I64, V]
     L.as_events_init.argtypes = [V, I32, V, V, I32, V, U64, I64, V]
     L.as_events_interval.argtypes = [V, I32, V, V, V, V, V, I32, C.c_float, V, V, U64, I64, V]
+    L.as_commands_step.argtypes = [V, I32, V, V, V, V, V, V, V, V, V, V, V, V, V, I32, C.c_float, V, U64, I64, V]
+    L.as_commands_reset.argtypes = [V, I32, V, V, V, V, V, V, V, V, V, I32, V, U64, I64, V]
     L.as_last_error.restype = C.c_char_p
     L.as_build_id.restype = C.c_char_p
     for name in EXPORTED_SYMBOLS:

@@ -879,6 +879,84 @@ int as_events_interval(const as_event_term_t* terms, int32_t num_terms, float* r
   return AS_OK;
 }
 
+static bool commands_shape_ok(int32_t num_terms, int32_t n, const std::string& what, std::string& err) {
+  if (num_terms < 1 || num_terms > AS_MAX_COMMAND_TERMS)
+    err = what + ": num_terms " + std::to_string(num_terms) + " outside [1, AS_MAX_COMMAND_TERMS = " +
+          std::to_string(AS_MAX_COMMAND_TERMS) + "]";
+  else if (n < 1 || n > AS_MAX_ENVS)
+    err = what + ": n " + std::to_string(n) + " outside [1, AS_MAX_ENVS]";
+  else
+    return true;
+  return false;
+}
+
+int as_commands_step(const as_command_term_t* terms, int32_t num_terms, const float* root_quat,
+                     const float* root_lin, const float* root_ang, float* vel, float* heading_target,
+                     uint8_t* flags, float* time_left, int32_t* counter, float* metrics, float* last_metrics,
+                     uint32_t* t, const uint8_t* reset, const uint8_t* reset2, int32_t n, float dt,
+                     const float* draws, uint64_t seed, int64_t env_id_offset, void* stream) {
+  if (!terms || !root_quat || !root_lin || !root_ang || !vel || !heading_target || !flags || !time_left || !counter ||
+      !metrics || !t)
+    return fail(AS_ERR_INVALID, "as_commands_step: null argument (terms / root_quat / root_lin / root_ang / vel / "
+                                "heading_target / flags / time_left / counter / metrics / t)");
+  std::string err;
+  if (!commands_shape_ok(num_terms, n, "as_commands_step", err)) return fail(AS_ERR_INVALID, err);
+  if (!(dt > 0.f) || !std::isfinite(dt))
+    return fail(AS_ERR_INVALID, "as_commands_step: dt " + std::to_string(dt) + " is not a positive finite step");
+  as::CommandsArgs a{};
+  a.terms = terms;
+  a.num_terms = num_terms;
+  a.n = n;
+  a.root_quat = root_quat;
+  a.root_lin = root_lin;
+  a.root_ang = root_ang;
+  a.vel = vel;
+  a.heading_target = heading_target;
+  a.flags = flags;
+  a.time_left = time_left;
+  a.counter = counter;
+  a.metrics = metrics;
+  a.last_metrics = last_metrics;
+  a.t = t;
+  a.reset = reset;
+  a.reset2 = reset2;
+  a.draws = draws;
+  a.dt = dt;
+  a.seed = seed;
+  a.env_offset = env_id_offset;
+  HIP_TRY(as::launch_commands_step(a, reinterpret_cast<hipStream_t>(stream)));
+  return AS_OK;
+}
+
+int as_commands_reset(const as_command_term_t* terms, int32_t num_terms, float* vel, float* heading_target,
+                      uint8_t* flags, float* time_left, int32_t* counter, float* metrics, float* last_metrics,
+                      uint32_t* t, const uint8_t* mask, int32_t n, const float* draws, uint64_t seed,
+                      int64_t env_id_offset, void* stream) {
+  if (!terms || !vel || !heading_target || !flags || !time_left || !counter || !metrics || !t)
+    return fail(AS_ERR_INVALID, "as_commands_reset: null argument (terms / vel / heading_target / flags / time_left / "
+                                "counter / metrics / t)");
+  std::string err;
+  if (!commands_shape_ok(num_terms, n, "as_commands_reset", err)) return fail(AS_ERR_INVALID, err);
+  as::CommandsArgs a{};
+  a.terms = terms;
+  a.num_terms = num_terms;
+  a.n = n;
+  a.vel = vel;
+  a.heading_target = heading_target;
+  a.flags = flags;
+  a.time_left = time_left;
+  a.counter = counter;
+  a.metrics = metrics;
+  a.last_metrics = last_metrics;
+  a.t = t;
+  a.reset = mask;
+  a.draws = draws;
+  a.seed = seed;
+  a.env_offset = env_id_offset;
+  HIP_TRY(as::launch_commands_reset(a, reinterpret_cast<hipStream_t>(stream)));
+  return AS_OK;
+}
+
 int as_set_graph_safe(as_env_t* env, int32_t on) {
   if (!env) return fail(AS_ERR_INVALID, "as_set_graph_safe: null handle");
   env->graph_safe = on != 0;

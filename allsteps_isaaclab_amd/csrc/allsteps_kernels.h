@@ -227,6 +227,30 @@ struct EventsArgs {
   int64_t env_offset;
 };
 
+// k_commands_step / k_commands_reset (as_commands_step / as_commands_reset, command_kernels.h): every buffer
+// field-major / env-minor.  k_commands_reset reads no root state, no dt and `reset` as its mask (null: every env)
+struct CommandsArgs {
+  const as_command_term_t* terms;  // [num_terms] device memory
+  int32_t num_terms, n;
+  const float* root_quat;          // [4][n]
+  const float* root_lin;           // [3][n]
+  const float* root_ang;           // [3][n]
+  float* vel;                      // [num_terms][3][n]
+  float* heading_target;           // [num_terms][n]
+  uint8_t* flags;                  // [num_terms][kCommandFlagRows][n]
+  float* time_left;                // [num_terms][n]
+  int32_t* counter;                // [num_terms][n]
+  float* metrics;                  // [num_terms][kCommandMetricRows][n]
+  float* last_metrics;             // [num_terms][kCommandMetricRows][n] or null: not written
+  uint32_t* t;                     // [n] per-env counter of the command streams
+  const uint8_t* reset;            // [n] or null
+  const uint8_t* reset2;           // [n] a second mask, ORed with the first, or null
+  const float* draws;              // [phases][num_terms][kCommandDraws][n] injected draws or null: Philox
+  float dt;
+  uint64_t seed;
+  int64_t env_offset;
+};
+
 // k_contact_timers (as_contact_timers, contact_timer_kernels.h): the air / contact timers over the contact
 // report; every buffer field-major / env-minor
 struct TimersArgs {
@@ -291,6 +315,8 @@ hipError_t launch_ray_camera(const CamArgs& a, hipStream_t stream);
 hipError_t launch_imu(const ImuArgs& a, hipStream_t stream);
 hipError_t launch_frame_transformer(const FrameTransformerArgs& a, hipStream_t stream);
 hipError_t launch_contact_timers(const TimersArgs& a, hipStream_t stream);
+hipError_t launch_commands_step(const CommandsArgs& a, hipStream_t stream);
+hipError_t launch_commands_reset(const CommandsArgs& a, hipStream_t stream);
 hipError_t launch_events_interval(const EventsArgs& a, hipStream_t stream);
 hipError_t launch_events_init(const EventsArgs& a, hipStream_t stream);
 hipError_t launch_noise_actions(const NoiseActArgs& a, hipStream_t stream);

@@ -27,7 +27,8 @@
 // after k_step: task_kernels.h (k_obs, k_stones, k_quad), body_state_kernel.h (k_body_state) and
 // contact_forces_kernel.h (k_contact_forces), noise_kernels.h, event_kernels.h, contact_timer_kernels.h
 // (k_contact_timers), ray_caster_kernels.h (k_ray_cast), imu_kernels.h (k_imu), ray_camera_kernels.h
-// (k_ray_camera) and frame_transformer_kernels.h (k_frame_transformer).
+// (k_ray_camera), frame_transformer_kernels.h (k_frame_transformer) and command_kernels.h (k_commands_step,
+// k_commands_reset).
 #include <hip/hip_runtime.h>
 
 #include "../../include/allsteps.h"
@@ -466,6 +467,7 @@ __global__ __launch_bounds__(kStepThreads) __attribute__((amdgpu_waves_per_eu(2,
 #include "imu_kernels.h"
 #include "frame_transformer_kernels.h"
 #include "ray_camera_kernels.h"
+#include "command_kernels.h"
 
 namespace as {
 
@@ -547,6 +549,18 @@ hipError_t launch_events_interval(const EventsArgs& a, hipStream_t stream) {
 hipError_t launch_events_init(const EventsArgs& a, hipStream_t stream) {
   hipLaunchKernelGGL(k_events_init, dim3((unsigned)((a.n + kEventThreads - 1) / kEventThreads)),
                      dim3(kEventThreads), 0, stream, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_commands_step(const CommandsArgs& a, hipStream_t stream) {
+  hipLaunchKernelGGL(k_commands_step, dim3((unsigned)((a.n + kCommandThreads - 1) / kCommandThreads)),
+                     dim3(kCommandThreads), 0, stream, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_commands_reset(const CommandsArgs& a, hipStream_t stream) {
+  hipLaunchKernelGGL(k_commands_reset, dim3((unsigned)((a.n + kCommandThreads - 1) / kCommandThreads)),
+                     dim3(kCommandThreads), 0, stream, a);
   return hipGetLastError();
 }
 

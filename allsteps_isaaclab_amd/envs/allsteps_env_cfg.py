@@ -118,6 +118,11 @@ class AllstepsEnvCfg:
     # (csrc/event_kernels.h), one launch more per step; anything else raises at construction.  None: the step as
     # ever.
     events: object = None
+    # Command manager (the reference's ManagerBasedRLEnvCfg `commands`): a dict or cfg object of utils.commands
+    # UniformVelocityCommandCfg / NormalVelocityCommandCfg terms, or None.  Served on the device by k_commands_step
+    # (csrc/command_kernels.h), one launch more per step, as env.command_manager; the task's observation and reward
+    # do not read it.  Anything else raises at construction.  None: nothing is allocated or launched.
+    commands: object = None
 
     # joint gears, cfg/PhysX dof order (allsteps_env_cfg.py:133-155)
     joint_gears: list = field(default_factory=lambda: [

@@ -104,6 +104,11 @@ class AnymalCStonesEnvCfg:
     observation_noise_model: object = None
     # interval events (as AllstepsEnvCfg's): a dict or cfg object of utils.events EventTermCfg or None
     events: object = None
+    # Command manager (the reference's ManagerBasedRLEnvCfg `commands`): a dict or cfg object of utils.commands
+    # UniformVelocityCommandCfg / NormalVelocityCommandCfg terms, or None.  Served on the device by k_commands_step
+    # (csrc/command_kernels.h), one launch more per step, as env.command_manager; the task's observation and reward
+    # do not read it.  Anything else raises at construction.  None: nothing is allocated or launched.
+    commands: object = None
 
     # the stepping-stone task (authored; include/allsteps.h as_quad_task_t): the ALLSTEPS target
     # machine and reward terms (allsteps_env.py:347-394, 418-457) on four feet

@@ -68,6 +68,16 @@ class DirectRLEnv:
                                   self.step_dt) if EnvEvents.wanted(cfg) else None)
         if self._events is not None:
             self.event_manager = EventManagerView(self._events)
+        # cfg.commands (the reference's CommandManager): device state of the command kernel and
+        # env.command_manager, or None -- then step() launches nothing for it and nothing is allocated
+        from .commands import EnvCommands
+
+        self._commands = (EnvCommands(cfg, self.num_envs, self._device, cfg.seed if cfg.seed is not None else 0,
+                                      self.step_dt) if EnvCommands.wanted(cfg) else None)
+        if self._commands is not None:
+            from .commands import CommandManagerView
+
+            self.command_manager = CommandManagerView(self._commands, self)
 
     # ------------------------------------------------------------------ properties
     @property
@@ -130,7 +140,10 @@ class DirectRLEnv:
         dones of the firing step are made from values cached before it.  With stateful sensors (the contact
         sensors' air / contact timers): their update for the step's substeps and the reset of the envs the step
         reset (:347, :361) follow the step directly.  Only ``step`` drives them -- a subclass's bare physics or
-        task launches do not.  With cfg.imu: every env's IMUs become outdated and their ``dt`` the physics step's, as
+        task launches do not.  With cfg.commands: the command terms' reset of the envs the step reset, then their
+        compute(step_dt), follow the step and the sensors and precede the interval events
+        (manager_based_rl_env.py:220-239); the commands read the root state and write only their own buffers, so
+        the step's outputs are those of an env without them.  With cfg.imu: every env's IMUs become outdated and their ``dt`` the physics step's, as
         after the reference's sensor updates (:347); nothing is launched until a sensor's data is read."""
         action = action.to(self._device)
         self._sim_step_counter += self.cfg.decimation
@@ -144,6 +157,9 @@ class DirectRLEnv:
             self._imus.mark_all(self.physics_dt)
         if self._sensors is not None:  # before the events, as a fixed order: the two touch disjoint buffers
             self._sensors.update(out[2], out[3])
+        if self._commands is not None:
+            self._commands.apply(*self._commands_root_state(), out[2], out[3], self._noise_offset(),
+                                 self._noise_stream())
         if self._events is not None:
             self._events.apply(*self._events_root_velocity(), self._noise_offset(), self._noise_stream())
         if nz is not None:
@@ -204,6 +220,8 @@ class DirectRLEnv:
             self._imus.mark(mask)
         for camera in self._cameras:  # RayCasterCamera.reset(env_ids): the envs' frame counters become zero
             camera.reset(None if mask is None else mask.bool())
+        if self._commands is not None:  # CommandManager.reset(env_ids) of _reset_idx: no compute
+            self._commands.reset(mask, self._noise_offset(), self._noise_stream())
 
     # ------------------------------------------------------------------ interval events
     def _events_root_velocity(self):
@@ -226,6 +244,24 @@ class DirectRLEnv:
         if self._events is not None:
             self._events.set_state(state)
         return {k: v for k, v in state.items() if k not in EnvEvents.STATE_KEYS}
+
+    # ------------------------------------------------------------------ command manager
+    def _commands_root_state(self):
+        """(root_quat (4, n), root_lin (3, n), root_ang (3, n)): the device rows the command terms read (subclass
+        hook)."""
+        raise NotImplementedError(f"{type(self).__name__} does not expose a root state for cfg.commands")
+
+    def _commands_get_state(self) -> dict:
+        """The command streams' counter and the terms' state for get_state (no keys without cfg.commands)."""
+        return {} if self._commands is None else self._commands.get_state()
+
+    def _commands_set_state(self, state: dict) -> dict:
+        """Load the command keys of a set_state dict; returns the dict without them."""
+        from .commands import EnvCommands
+
+        if self._commands is not None:
+            self._commands.set_state(state)
+        return {k: v for k, v in state.items() if k not in EnvCommands.STATE_KEYS}
 
     @staticmethod
     def seed(seed: int = -1) -> int:
@@ -264,12 +300,15 @@ class DirectRLEnv:
 
     # ------------------------------------------------------------------ subclass hooks
     def _reseed(self, seed: int):
-        """Re-seed the device streams (subclasses extend it): here the Philox key of the noise models and of
-        the interval events (whose timers stay as they are: DirectRLEnv never resets the event manager)."""
+        """Re-seed the device streams (subclasses extend it): here the Philox key of the noise models, of
+        the interval events (whose timers stay as they are: DirectRLEnv never resets the event manager) and of the
+        command terms."""
         if self._noise is not None:
             self._noise.seed = int(seed)
         if self._events is not None:
             self._events.seed = int(seed)
+        if self._commands is not None:
+            self._commands.seed = int(seed)
 
     def _reset_impl(self):
         raise NotImplementedError

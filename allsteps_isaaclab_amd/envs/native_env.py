@@ -96,6 +96,9 @@ class NativeDirectEnv(DirectRLEnv):
     def _events_root_velocity(self):
         return self.state["root_lin"], self.state["root_ang"]
 
+    def _commands_root_state(self):
+        return self.state["root_quat"], self.state["root_lin"], self.state["root_ang"]
+
     def _report_or_raise(self, what: str) -> _ContactReport:
         if self._report is None:
             raise _native.NativeError(
@@ -122,10 +125,13 @@ class NativeDirectEnv(DirectRLEnv):
         stream's counter and biases (noise_t, noise_action_bias, noise_obs_bias); with cfg.events, the event
         streams' counter and timers (event_t, event_time_left); with cfg.contact_air_time, the sensors' timers and
         timestamp (contact_timers (4, B, N), contact_timestamp (N,)); with cfg.imu, the IMUs' previous world
-        velocities (imu_prev_lin_vel, imu_prev_ang_vel, (3, S, N) each)."""
+        velocities (imu_prev_lin_vel, imu_prev_ang_vel, (3, S, N) each); with cfg.commands, the command streams'
+        counter and the terms' state (command_t, command_time_left, command_vel_b, command_heading_target,
+        command_flags, command_counter, command_metrics, command_last_metrics)."""
         tm, im = self._contact_timers, self._imus
         return {**{k: v.clone() for k, v in self.state.items()}, **self._noise_get_state(),
-                **self._events_get_state(), **({} if tm is None else tm.get_state()),
+                **self._events_get_state(), **self._commands_get_state(),
+                **({} if tm is None else tm.get_state()),
                 **({} if im is None else im.get_state())}
 
     def set_state(self, state: dict):
@@ -135,7 +141,7 @@ class NativeDirectEnv(DirectRLEnv):
         if self._imus is not None:  # (and every env is outdated)
             self._imus.set_state(state)
         state = {k: v for k, v in state.items() if k not in _ContactTimers.STATE_KEYS + _ImuSet.STATE_KEYS}
-        for k, v in self._events_set_state(self._noise_set_state(state)).items():
+        for k, v in self._commands_set_state(self._events_set_state(self._noise_set_state(state))).items():
             self.state[k].copy_(torch.as_tensor(v).to(self.state[k].device, self.state[k].dtype).reshape(
                 self.state[k].shape))
 

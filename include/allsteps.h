@@ -564,6 +564,56 @@ int as_events_interval(const as_event_term_t* terms, int32_t num_terms, float* r
                        const float* interval_draws, const float* push_draws, uint64_t seed, int64_t env_id_offset,
                        void* stream);
 
+/* Command manager, off by default: the velocity command terms of cfg.commands (isaaclab/managers/
+ * command_manager.py; UniformVelocityCommand / NormalVelocityCommand, isaaclab/envs/mdp/commands/
+ * velocity_command.py).  The reference's step resets the envs that are done, then calls
+ * command_manager.compute(step_dt), then applies the interval events (manager_based_rl_env.py:220-239): the caller
+ * launches as_commands_step after as_step and before as_events_interval on the same stream.  Stateless entry
+ * points over caller-owned device buffers, as the events' -- no as_env_t.  Every buffer is field-major /
+ * env-minor: root_quat [4][n] (w x y z), root_lin [3][n], root_ang [3][n] (as_state_t's, read only), vel
+ * [num_terms][3][n], heading_target [num_terms][n], flags [num_terms][5][n] uint8 (is_heading, is_standing,
+ * is_zero_vel_x / y / yaw), time_left [num_terms][n], counter [num_terms][n] int32, metrics and last_metrics
+ * [num_terms][2][n] (error_vel_xy, error_vel_yaw), t [n] (the per-env counter of the command streams).
+ * Semantics, the float32 rounding order and the Philox stream layout (seed, env_id_offset + e, t[e], term block,
+ * phase tag): csrc/allsteps_commands.h.  Both calls are graph-safe: nothing per call comes from the host but the
+ * pointers and the fixed dt; the term descriptors are read from device memory at every launch.  The host forms
+ * every constant of a descriptor (envs/commands.py). */
+#define AS_MAX_COMMAND_TERMS 4
+#define AS_COMMAND_DRAWS 11 /* draws a term consumes per resample at most (csrc/allsteps_commands.h) */
+enum { AS_COMMAND_UNIFORM = 0, AS_COMMAND_NORMAL = 1 };
+typedef struct {
+  int32_t kind;             /* AS_COMMAND_UNIFORM / AS_COMMAND_NORMAL */
+  int32_t heading;          /* heading_command (uniform term only) */
+  float time_lo, time_w;    /* resampling_time_range: float32(lo), float32(hi) - float32(lo) */
+  float lo[4], w[4];        /* uniform: lin_vel_x, lin_vel_y, ang_vel_z, heading as float32(lo), float32(hi) -
+                               float32(lo); normal: mean_vel in lo[0..2], std_vel in w[0..2] */
+  float clip_lo, clip_hi;   /* ang_vel_z as float32: the heading controller's clip */
+  float stiffness;          /* heading_control_stiffness */
+  float p_heading;          /* rel_heading_envs */
+  float p_standing;         /* rel_standing_envs */
+  float p_zero[3];          /* zero_prob (normal term) */
+  float max_command_step;   /* float32(resampling_time_range[1] / step_dt), the division in double */
+} as_command_term_t;
+/* One env step of every term in one launch, terms in order.  For an env with reset[e] | reset2[e] != 0 ([n] uint8
+ * each, either may be NULL: no env): CommandTerm.reset -- last_metrics = metrics, metrics = 0, counter = 0,
+ * resample.  Then for every env CommandTerm.compute(dt): metrics, time_left -= dt, resample where time_left <= 0,
+ * the command's update.  Then t[e] += 1.  draws: NULL (Philox) or [2][num_terms][AS_COMMAND_DRAWS][n] injected
+ * draws, phase 0 the reset's and phase 1 the compute's, read only where a term resamples -- uniforms in [0, 1),
+ * and unit normals in rows 1..3 of a normal term.  last_metrics may be NULL: not written.
+ * 1 <= num_terms <= AS_MAX_COMMAND_TERMS. */
+int as_commands_step(const as_command_term_t* terms, int32_t num_terms, const float* root_quat,
+                     const float* root_lin, const float* root_ang, float* vel, float* heading_target,
+                     uint8_t* flags, float* time_left, int32_t* counter, float* metrics, float* last_metrics,
+                     uint32_t* t, const uint8_t* reset, const uint8_t* reset2, int32_t n, float dt,
+                     const float* draws, uint64_t seed, int64_t env_id_offset, void* stream);
+/* CommandTerm.reset alone, no compute (ManagerBasedRLEnv.reset, command_manager.reset(env_ids)): for the envs
+ * with mask[e] != 0 ([n] uint8; NULL: every env), then t[e] += 1 for every env.  draws: NULL or
+ * [num_terms][AS_COMMAND_DRAWS][n]. */
+int as_commands_reset(const as_command_term_t* terms, int32_t num_terms, float* vel, float* heading_target,
+                      uint8_t* flags, float* time_left, int32_t* counter, float* metrics, float* last_metrics,
+                      uint32_t* t, const uint8_t* mask, int32_t n, const float* draws, uint64_t seed,
+                      int64_t env_id_offset, void* stream);
+
 /* The H^-1 sweep plan for a model (round 6, ABI 5; no device needed). The step kernel sweeps the
  * padded joint-space inertia last block first and, for the trees it is compiled for (the walker, the
  * C5 quadruped), skips the column quads in which the pivot rows are structurally zero -- an exact
