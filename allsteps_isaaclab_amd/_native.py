@@ -28,7 +28,8 @@ EXPORTED_SYMBOLS = [
     "as_build_id", "as_step_counters_host", "as_body_state", "as_sweep_plan", "as_set_contact_report",
     "as_contact_forces", "as_noise_actions", "as_noise_post", "as_events_init", "as_events_interval",
     "as_contact_timers", "as_ray_cast", "as_imu", "as_ray_camera",
-    "as_frame_transformer", "as_commands_step", "as_commands_reset",
+    "as_frame_transformer", "as_commands_step", "as_commands_reset", "as_observations_step",
+    "as_observations_reset",
 ]
 MAXB = 32  # AS_MAX_BODIES
 MAXC = 10  # AS_MAX_CONTACTS
@@ -202,6 +203,57 @@ def commands_reset(terms, vel, heading_target, flags, time_left, counter, metric
                                    time_left.data_ptr(), counter.data_ptr(), metrics.data_ptr(), _ptr(last_metrics),
                                    t.data_ptr(), _ptr(mask), n, _ptr(draws), seed & 0xFFFFFFFFFFFFFFFF, env_offset,
                                    stream), "as_commands_reset")
+
+
+MAX_OBS_GROUPS = 4  # AS_MAX_OBS_GROUPS
+MAX_OBS_TERMS = 16  # AS_MAX_OBS_TERMS: terms of a group
+MAX_OBS_COLS = 256  # AS_MAX_OBS_COLS: columns of a group before the history
+MAX_OBS_OUT_COLS = 1280  # AS_MAX_OBS_OUT_COLS: columns of a group's output, history included
+OBS_COL_ROWS = 6  # AS_OBS_COL_ROWS: source row (int32) | a | b | noise p0 | noise p1 | scale
+OBS_GATHER, OBS_LIMIT_NORM, OBS_QUAT_UNIQUE, OBS_ROTATE_INVERSE, OBS_HEIGHT_SCAN, OBS_LAST_ACTION = range(6)  # AS_OBS_*
+OBS_SOURCES = ("root_pos", "root_quat", "root_lin", "root_ang", "q", "qd", "commands", "imu", "ray_hits", "ray_pose",
+               "actions", "gravity")  # AS_OBS_SRC_*, in order
+# as_observation_term_t as 12 32-bit words: kind, source, width, col, out_col, history, noise_kind, noise_op, clip
+# (int32) | clip_lo, clip_hi (float32) | flags (int32)
+OBS_TERM_WORDS = 12
+OBS_TAG = 0x4F62734D  # Philox tag of the observation streams (csrc/allsteps_observations.h)
+
+
+class AsObservationSources(C.Structure):
+    """as_observation_sources_t (include/allsteps.h): the device rows the terms of a group read."""
+    _fields_ = [("ptr", C.c_void_p * len(OBS_SOURCES)), ("rows", C.c_int32 * len(OBS_SOURCES))]
+
+
+def make_observation_sources(tensors: dict) -> AsObservationSources:
+    """as_observation_sources_t over {source name: tensor}: field-major (rows, ..., n) tensors, the actions (n, A)."""
+    S = AsObservationSources()
+    for k, name in enumerate(OBS_SOURCES):
+        t = tensors.get(name)
+        if t is None:
+            continue
+        S.ptr[k] = t.data_ptr()
+        S.rows[k] = t.shape[1] if name == "actions" else t.numel() // t.shape[-1]
+    return S
+
+
+def observations_step(terms, cols, omap, d0: int, out_cols: int, group: int, sources: AsObservationSources, out,
+                      count, t, reset=None, reset2=None, draws=None, seed: int = 0, env_offset: int = 0, stream=None):
+    """as_observations_step: one group, one launch.  terms (num_terms, 12) float32 device rows of
+    as_observation_term_t, cols (6, 256) float32 words, omap (out_cols,) int32; out (n, out_cols), count (n,) int32,
+    t (n,) int32; reset / reset2 (n,) uint8 / bool or None; draws (d0, n) injected or None (Philox)."""
+    n = out.shape[0]
+    check(load().as_observations_step(terms.data_ptr(), terms.shape[0], cols.data_ptr(), omap.data_ptr(), d0,
+                                      out_cols, group, C.byref(sources), out.data_ptr(), count.data_ptr(),
+                                      t.data_ptr(), _ptr(reset), _ptr(reset2), n, _ptr(draws),
+                                      seed & 0xFFFFFFFFFFFFFFFF, env_offset, stream), "as_observations_step")
+
+
+def observations_reset(out, count, mask=None, stream=None):
+    """as_observations_reset: the push count and the output row of the envs in mask ((n,) uint8 / bool, None: all)
+    become 0."""
+    n, out_cols = out.shape
+    check(load().as_observations_reset(out.data_ptr(), out_cols, count.data_ptr(), _ptr(mask), n, stream),
+          "as_observations_reset")
 
 
 def unpack_report_ids(w):
@@ -382,6 +434,8 @@ def load() -> C.CDLL:
     L.as_events_interval.argtypes = [V, I32, V, V, V, V, V, I32, C.c_float, V, V, U64, I64, V]
     L.as_commands_step.argtypes = [V, I32, V, V, V, V, V, V, V, V, V, V, V, V, V, I32, C.c_float, V, U64, I64, V]
     L.as_commands_reset.argtypes = [V, I32, V, V, V, V, V, V, V, V, V, I32, V, U64, I64, V]
+    L.as_observations_step.argtypes = [V, I32, V, V, I32, I32, I32, V, V, V, V, V, V, I32, V, U64, I64, V]
+    L.as_observations_reset.argtypes = [V, I32, V, V, I32, V]
     L.as_last_error.restype = C.c_char_p
     L.as_build_id.restype = C.c_char_p
     for name in EXPORTED_SYMBOLS:

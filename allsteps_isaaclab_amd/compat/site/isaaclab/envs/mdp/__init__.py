@@ -1,13 +1,20 @@
 """Shim of ``isaaclab.envs.mdp``: the event function the device event kernel serves, the height-scan
 observation over the device ray caster, the image observation over the device ray-cast camera, the IMU
-observations over the device IMU kernel, and the velocity command cfgs and ``generated_commands`` over the device
-command kernel."""
+observations over the device IMU kernel, the velocity command cfgs and ``generated_commands`` over the device
+command kernel, and the observation functions the device observation kernel serves."""
 
 from allsteps_isaaclab_amd.utils.commands import (  # noqa: F401
     NormalVelocityCommandCfg, NullCommandCfg, UniformVelocityCommandCfg, generated_commands)
 from allsteps_isaaclab_amd.utils.events import push_by_setting_velocity  # noqa: F401
+from allsteps_isaaclab_amd.utils.observations import (  # noqa: F401
+    base_ang_vel, base_lin_vel, base_pos_z, body_incoming_wrench, image_features, joint_pos,
+    joint_pos_limit_normalized, joint_pos_rel, joint_vel, joint_vel_rel, last_action, projected_gravity, root_ang_vel_w,
+    root_lin_vel_w, root_pos_w, root_quat_w)
 from allsteps_isaaclab_amd.utils.sensors import (  # noqa: F401
     height_scan, image, imu_ang_vel, imu_lin_acc, imu_orientation)
 
 __all__ = ["push_by_setting_velocity", "height_scan", "image", "imu_orientation", "imu_ang_vel", "imu_lin_acc",
-           "UniformVelocityCommandCfg", "NormalVelocityCommandCfg", "NullCommandCfg", "generated_commands"]
+           "UniformVelocityCommandCfg", "NormalVelocityCommandCfg", "NullCommandCfg", "generated_commands",
+           "base_pos_z", "base_lin_vel", "base_ang_vel", "projected_gravity", "root_pos_w", "root_quat_w",
+           "root_lin_vel_w", "root_ang_vel_w", "joint_pos", "joint_pos_rel", "joint_pos_limit_normalized", "joint_vel",
+           "joint_vel_rel", "last_action", "body_incoming_wrench", "image_features"]

@@ -957,6 +957,68 @@ int as_commands_reset(const as_command_term_t* terms, int32_t num_terms, float* 
   return AS_OK;
 }
 
+int as_observations_step(const as_observation_term_t* terms, int32_t num_terms, const float* cols,
+                         const int32_t* omap, int32_t d0, int32_t out_cols, int32_t group,
+                         const as_observation_sources_t* sources, float* out, int32_t* count, uint32_t* t,
+                         const uint8_t* reset, const uint8_t* reset2, int32_t n, const float* draws, uint64_t seed,
+                         int64_t env_id_offset, void* stream) {
+  if (!terms || !cols || !omap || !sources || !out || !count || !t)
+    return fail(AS_ERR_INVALID, "as_observations_step: null argument (terms / cols / omap / sources / out / count / "
+                                "t)");
+  if (num_terms < 1 || num_terms > AS_MAX_OBS_TERMS)
+    return fail(AS_ERR_INVALID, "as_observations_step: num_terms " + std::to_string(num_terms) +
+                                    " outside [1, AS_MAX_OBS_TERMS = " + std::to_string(AS_MAX_OBS_TERMS) + "]");
+  if (d0 < 1 || d0 > AS_MAX_OBS_COLS || out_cols < d0 || out_cols > AS_MAX_OBS_OUT_COLS)
+    return fail(AS_ERR_INVALID, "as_observations_step: " + std::to_string(d0) + " columns (at most AS_MAX_OBS_COLS = " +
+                                    std::to_string(AS_MAX_OBS_COLS) + "), " + std::to_string(out_cols) +
+                                    " with history (at most AS_MAX_OBS_OUT_COLS = " +
+                                    std::to_string(AS_MAX_OBS_OUT_COLS) + ")");
+  if (group < 0 || group >= AS_MAX_OBS_GROUPS)
+    return fail(AS_ERR_INVALID, "as_observations_step: group " + std::to_string(group) +
+                                    " outside [0, AS_MAX_OBS_GROUPS)");
+  if (n < 1 || n > AS_MAX_ENVS) return fail(AS_ERR_INVALID, "as_observations_step: n outside [1, AS_MAX_ENVS]");
+  for (int s = 0; s < AS_OBS_NUM_SOURCES; ++s)
+    if (sources->rows[s] < 0 || (sources->ptr[s] && sources->rows[s] < 1))
+      return fail(AS_ERR_INVALID, "as_observations_step: source " + std::to_string(s) + " has no rows");
+  as::ObservationsArgs a{};
+  a.terms = terms;
+  a.cols = cols;
+  a.omap = omap;
+  a.num_terms = num_terms;
+  a.d0 = d0;
+  a.out_cols = out_cols;
+  a.group = group;
+  a.n = n;
+  a.src = *sources;
+  a.out = out;
+  a.count = count;
+  a.t = t;
+  a.reset = reset;
+  a.reset2 = reset2;
+  a.draws = draws;
+  a.seed = seed;
+  a.env_offset = env_id_offset;
+  HIP_TRY(as::launch_observations(a, reinterpret_cast<hipStream_t>(stream)));
+  return AS_OK;
+}
+
+int as_observations_reset(float* out, int32_t out_cols, int32_t* count, const uint8_t* mask, int32_t n,
+                          void* stream) {
+  if (!out || !count) return fail(AS_ERR_INVALID, "as_observations_reset: null argument (out / count)");
+  if (out_cols < 1 || out_cols > AS_MAX_OBS_OUT_COLS)
+    return fail(AS_ERR_INVALID, "as_observations_reset: out_cols " + std::to_string(out_cols) +
+                                    " outside [1, AS_MAX_OBS_OUT_COLS]");
+  if (n < 1 || n > AS_MAX_ENVS) return fail(AS_ERR_INVALID, "as_observations_reset: n outside [1, AS_MAX_ENVS]");
+  as::ObservationsArgs a{};
+  a.out = out;
+  a.out_cols = out_cols;
+  a.count = count;
+  a.reset = mask;
+  a.n = n;
+  HIP_TRY(as::launch_observations_reset(a, reinterpret_cast<hipStream_t>(stream)));
+  return AS_OK;
+}
+
 int as_set_graph_safe(as_env_t* env, int32_t on) {
   if (!env) return fail(AS_ERR_INVALID, "as_set_graph_safe: null handle");
   env->graph_safe = on != 0;

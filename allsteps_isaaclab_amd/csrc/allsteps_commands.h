@@ -59,6 +59,7 @@
 
 #include "../../include/allsteps.h"
 #include "../../include/as_detmath.h"
+#include "allsteps_base_frame.h"
 #include "allsteps_noise.h"
 
 // the short loops over components are unrolled on the device, so that the draws and the state stay in registers
@@ -153,47 +154,11 @@ AS_NZ_FN void command_reset_head(CommandState& s, float (&last_metrics)[kCommand
   s.counter = 0;
 }
 
-// torch.cross / Tensor.cross: the kernel's a1 b2 - a2 b1 is compiled as one fused multiply-add over the rounded
-// second product (established against torch by the fixture: the separately rounded form misses its bits)
-AS_NZ_FN void command_cross(const float (&a)[3], const float (&b)[3], float (&o)[3]) {
-  o[0] = fmaf(a[1], b[2], -(a[2] * b[1]));
-  o[1] = fmaf(a[2], b[0], -(a[0] * b[2]));
-  o[2] = fmaf(a[0], b[1], -(a[1] * b[0]));
-}
-
-// math.py:606-625, the dot product (a bmm) in the order (x u0 + y u1) + z u2, each operation rounded
-AS_NZ_FN void command_rotate_inverse(const float (&q)[4], const float (&u)[3], float (&o)[3]) {
-  const float qw = q[0];
-  const float xyz[3] = {q[1], q[2], q[3]};
-  const float s = 2.0f * (qw * qw) - 1.0f;
-  float x[3];
-  command_cross(xyz, u, x);
-  const float dot = (xyz[0] * u[0] + xyz[1] * u[1]) + xyz[2] * u[2];
-  AS_CMD_UNROLL
-  for (int k = 0; k < 3; ++k) {
-    const float a = u[k] * s;
-    const float b = (x[k] * qw) * 2.0f;
-    const float cc = (xyz[k] * dot) * 2.0f;
-    o[k] = (a - b) + cc;
-  }
-}
-
-// articulation_data.py heading_w: quat_apply(q, (1, 0, 0)) (math.py:546-564), then atan2(fwd.y, fwd.x)
-AS_NZ_FN void command_forward(const float (&q)[4], float (&fwd)[3]) {
-  const float xyz[3] = {q[1], q[2], q[3]};
-  const float v[3] = {1.0f, 0.0f, 0.0f};
-  float t[3], x[3];
-  command_cross(xyz, v, t);
-  AS_CMD_UNROLL
-  for (int k = 0; k < 3; ++k) t[k] = t[k] * 2.0f;
-  command_cross(xyz, t, x);
-  AS_CMD_UNROLL
-  for (int k = 0; k < 3; ++k) fwd[k] = (v[k] + q[0] * t[k]) + x[k];
-}
-
+// the base-frame expressions (cross, quat_rotate_inverse, the heading's forward vector): allsteps_base_frame.h,
+// shared with the observation terms
 AS_NZ_FN float command_heading_w(const float (&q)[4]) {
   float fwd[3];
-  command_forward(q, fwd);
+  base_forward(q, fwd);
   return as_atan2f(fwd[1], fwd[0]);
 }
 
@@ -208,8 +173,8 @@ AS_NZ_FN float command_wrap_to_pi(float a) {
 AS_NZ_FN void command_update_metrics(const as_command_term_t& c, CommandState& s, const float (&q)[4],
                                      const float (&lin)[3], const float (&ang)[3]) {
   float lin_b[3], ang_b[3];
-  command_rotate_inverse(q, lin, lin_b);
-  command_rotate_inverse(q, ang, ang_b);
+  base_rotate_inverse(q, lin, lin_b);
+  base_rotate_inverse(q, ang, ang_b);
   const float dx = s.vel[0] - lin_b[0], dy = s.vel[1] - lin_b[1];
   // torch.norm over the two components accumulates acc = fma(x, x, acc) from 0: dx dx rounded, then one fused step
   s.metrics[kCmdErrXY] = s.metrics[kCmdErrXY] + sqrtf(fmaf(dy, dy, dx * dx)) / c.max_command_step;

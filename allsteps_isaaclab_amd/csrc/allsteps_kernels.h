@@ -227,6 +227,25 @@ struct EventsArgs {
   int64_t env_offset;
 };
 
+// k_observations / k_observations_reset (as_observations_step / as_observations_reset, observation_kernels.h): one
+// group of cfg.observations.  k_observations_reset reads out, out_cols, count, n and `reset` as its mask (null: every
+// env) only
+struct ObservationsArgs {
+  const as_observation_term_t* terms;  // [num_terms] device memory
+  const float* cols;                   // [AS_OBS_COL_ROWS][AS_MAX_OBS_COLS] 32-bit words, device memory
+  const int32_t* omap;                 // [out_cols] device memory
+  int32_t num_terms, d0, out_cols, group, n;
+  as_observation_sources_t src;
+  float* out;                          // [n][out_cols]
+  int32_t* count;                      // [n] pushes since the env's reset
+  uint32_t* t;                         // [n] per-env counter of the group's stream
+  const uint8_t* reset;                // [n] or null
+  const uint8_t* reset2;               // [n] a second mask, ORed with the first, or null
+  const float* draws;                  // [d0][n] injected draws or null: Philox
+  uint64_t seed;
+  int64_t env_offset;
+};
+
 // k_commands_step / k_commands_reset (as_commands_step / as_commands_reset, command_kernels.h): every buffer
 // field-major / env-minor.  k_commands_reset reads no root state, no dt and `reset` as its mask (null: every env)
 struct CommandsArgs {
@@ -317,6 +336,8 @@ hipError_t launch_frame_transformer(const FrameTransformerArgs& a, hipStream_t s
 hipError_t launch_contact_timers(const TimersArgs& a, hipStream_t stream);
 hipError_t launch_commands_step(const CommandsArgs& a, hipStream_t stream);
 hipError_t launch_commands_reset(const CommandsArgs& a, hipStream_t stream);
+hipError_t launch_observations(const ObservationsArgs& a, hipStream_t stream);
+hipError_t launch_observations_reset(const ObservationsArgs& a, hipStream_t stream);
 hipError_t launch_events_interval(const EventsArgs& a, hipStream_t stream);
 hipError_t launch_events_init(const EventsArgs& a, hipStream_t stream);
 hipError_t launch_noise_actions(const NoiseActArgs& a, hipStream_t stream);

@@ -27,8 +27,8 @@
 // after k_step: task_kernels.h (k_obs, k_stones, k_quad), body_state_kernel.h (k_body_state) and
 // contact_forces_kernel.h (k_contact_forces), noise_kernels.h, event_kernels.h, contact_timer_kernels.h
 // (k_contact_timers), ray_caster_kernels.h (k_ray_cast), imu_kernels.h (k_imu), ray_camera_kernels.h
-// (k_ray_camera), frame_transformer_kernels.h (k_frame_transformer) and command_kernels.h (k_commands_step,
-// k_commands_reset).
+// (k_ray_camera), frame_transformer_kernels.h (k_frame_transformer), command_kernels.h (k_commands_step,
+// k_commands_reset) and observation_kernels.h (k_observations, k_observations_reset).
 #include <hip/hip_runtime.h>
 
 #include "../../include/allsteps.h"
@@ -468,6 +468,7 @@ __global__ __launch_bounds__(kStepThreads) __attribute__((amdgpu_waves_per_eu(2,
 #include "frame_transformer_kernels.h"
 #include "ray_camera_kernels.h"
 #include "command_kernels.h"
+#include "observation_kernels.h"
 
 namespace as {
 
@@ -549,6 +550,18 @@ hipError_t launch_events_interval(const EventsArgs& a, hipStream_t stream) {
 hipError_t launch_events_init(const EventsArgs& a, hipStream_t stream) {
   hipLaunchKernelGGL(k_events_init, dim3((unsigned)((a.n + kEventThreads - 1) / kEventThreads)),
                      dim3(kEventThreads), 0, stream, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_observations(const ObservationsArgs& a, hipStream_t stream) {
+  hipLaunchKernelGGL(k_observations, dim3((unsigned)((a.n + kObsTile - 1) / kObsTile)), dim3(kObsThreads), 0, stream,
+                     a);
+  return hipGetLastError();
+}
+
+hipError_t launch_observations_reset(const ObservationsArgs& a, hipStream_t stream) {
+  hipLaunchKernelGGL(k_observations_reset, dim3((unsigned)((a.n + kObsTile - 1) / kObsTile)), dim3(kObsThreads), 0,
+                     stream, a);
   return hipGetLastError();
 }
 

@@ -73,6 +73,9 @@ class AllstepsEnv(NativeDirectEnv):
         self.right_body_indices = L(cfg.right_body_names)
         self.left_body_indices = L(cfg.left_body_names)
         self.negation_body_indices = L(cfg.negation_body_names)
+        self._observations_start()
+
+    _actions_clamped = True  # `actions` below
 
     # ------------------------------------------------------------------ task buffers (views)
     curr_target_index = property(lambda self: self.state["idx"])

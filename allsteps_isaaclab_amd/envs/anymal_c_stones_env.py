@@ -75,6 +75,13 @@ class AnymalCStonesEnv(NativeDirectEnv):
         # the ArticulationData views (ring 1 zero-copy, ring 2 -- the 13 MJCF bodies -- by as_body_state on
         # demand), as the walker's env serves them (envs/views.py)
         self.robot = _RobotView(self, default_joint_pos=self.default_joint_pos)
+        self._actions = torch.zeros(n, self.num_dof, dtype=torch.float32, device=dev)
+        self._observations_start()
+
+    @property
+    def actions(self) -> torch.Tensor:
+        """The last step's actions as the step took them (anymal_c_env.py keeps them unclamped)."""
+        return self._actions
 
     @property
     def target_index(self) -> torch.Tensor:
@@ -118,5 +125,6 @@ class AnymalCStonesEnv(NativeDirectEnv):
         self._native.quad_step(a, self.obs_buf, self.reward_buf, self.reset_terminated, self.reset_time_outs,
                                stream=self._stream())
         self._launches += 1
+        self._actions = a
         self._reset_buf_stale = True
         return {"policy": self.obs_buf}, self.reward_buf, self.reset_terminated, self.reset_time_outs, self.extras

@@ -109,6 +109,12 @@ class AnymalCStonesEnvCfg:
     # (csrc/command_kernels.h), one launch more per step, as env.command_manager; the task's observation and reward
     # do not read it.  Anything else raises at construction.  None: nothing is allocated or launched.
     commands: object = None
+    # Observation manager (the reference's ManagerBasedEnvCfg `observations`): a dict or cfg object whose entries are
+    # utils.observations ObservationGroupCfg groups of ObservationTermCfg terms, or None.  Each group is assembled on
+    # the device by k_observations (csrc/observation_kernels.h), one launch per group last in the step, as
+    # env.observation_manager and under its name in the returned observation dict; "policy" stays the task's own.
+    # Anything not served raises at construction.  None: nothing is allocated or launched.
+    observations: object = None
 
     # the stepping-stone task (authored; include/allsteps.h as_quad_task_t): the ALLSTEPS target
     # machine and reward terms (allsteps_env.py:347-394, 418-457) on four feet

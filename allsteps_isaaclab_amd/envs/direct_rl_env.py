@@ -40,6 +40,9 @@ class DirectRLEnv:
     # outdated by time and by reset only, env by env (a recompute moves their previous velocities).  None: nothing
     # to mark.
     _imus = None
+    # cfg.observations (the reference's ObservationManager): the device state of the observation kernel, built by
+    # _observations_start once the subclass has its views.  None: step() launches nothing for it.
+    _observations = None
 
     def __init__(self, cfg, render_mode: str | None = None, **kwargs):
         self.cfg = cfg
@@ -129,6 +132,8 @@ class DirectRLEnv:
         self._scene_changed()
         self._sensors_reset(None)
         self._noise_reset(None)  # the returned observation is not noised (direct_rl_env.py:294)
+        if self._observations is not None:  # every history was reset (_sensors_reset); one compute fills them
+            obs.update(self._observations.compute_all_reset())
         return obs, self.extras
 
     def step(self, action: torch.Tensor):
@@ -144,7 +149,11 @@ class DirectRLEnv:
         compute(step_dt), follow the step and the sensors and precede the interval events
         (manager_based_rl_env.py:220-239); the commands read the root state and write only their own buffers, so
         the step's outputs are those of an env without them.  With cfg.imu: every env's IMUs become outdated and their ``dt`` the physics step's, as
-        after the reference's sensor updates (:347); nothing is launched until a sensor's data is read."""
+        after the reference's sensor updates (:347); nothing is launched until a sensor's data is read.  With
+        cfg.observations: the term groups are assembled last, one launch per group, after the sensors their terms
+        read were brought up to date (manager_based_rl_env.py step: the observations follow the reset, the commands
+        and the interval events); they join the returned observation dict under their group names and write only
+        their own buffers."""
         action = action.to(self._device)
         self._sim_step_counter += self.cfg.decimation
         nz = self._noise
@@ -164,6 +173,8 @@ class DirectRLEnv:
             self._events.apply(*self._events_root_velocity(), self._noise_offset(), self._noise_stream())
         if nz is not None:
             nz.post(out[0]["policy"], out[2], out[3], self._noise_offset(), self._noise_stream())
+        if self._observations is not None:
+            out[0].update(self._observations.compute(out[2], out[3]))
         self.common_step_counter += 1
         return out
 
@@ -222,6 +233,8 @@ class DirectRLEnv:
             camera.reset(None if mask is None else mask.bool())
         if self._commands is not None:  # CommandManager.reset(env_ids) of _reset_idx: no compute
             self._commands.reset(mask, self._noise_offset(), self._noise_stream())
+        if self._observations is not None:  # ObservationManager.reset(env_ids): the histories, no compute
+            self._observations.reset(mask)
 
     # ------------------------------------------------------------------ interval events
     def _events_root_velocity(self):
@@ -263,6 +276,38 @@ class DirectRLEnv:
             self._commands.set_state(state)
         return {k: v for k, v in state.items() if k not in EnvCommands.STATE_KEYS}
 
+    # ------------------------------------------------------------------ observation manager
+    def _observations_start(self) -> None:
+        """Build the observation manager of cfg.observations once the subclass has its state, views and sensors
+        (the last line of its constructor); raises NativeError for a cfg the kernel does not serve."""
+        from .observations import EnvObservations, ObservationManagerView
+
+        if EnvObservations.wanted(self.cfg):
+            self._observations = EnvObservations(self.cfg, self, self.num_envs, self._device,
+                                                 self.cfg.seed if self.cfg.seed is not None else 0)
+            self.observation_manager = ObservationManagerView(self._observations)
+
+    def _observations_context(self):
+        """The ObsContext of the env: what its terms can read (subclass hook)."""
+        raise NotImplementedError(f"{type(self).__name__} does not serve cfg.observations")
+
+    def _observations_sources(self) -> dict:
+        """{source name: device tensor} of the rows the terms read (subclass hook)."""
+        raise NotImplementedError(f"{type(self).__name__} does not serve cfg.observations")
+
+    def _observations_get_state(self) -> dict:
+        """The observation streams' counters, the push counts and the histories (no keys without
+        cfg.observations)."""
+        return {} if self._observations is None else self._observations.get_state()
+
+    def _observations_set_state(self, state: dict) -> dict:
+        """Load the observation keys of a set_state dict; returns the dict without them."""
+        from .observations import EnvObservations
+
+        if self._observations is not None:
+            self._observations.set_state(state)
+        return {k: v for k, v in state.items() if not EnvObservations.is_state_key(k)}
+
     @staticmethod
     def seed(seed: int = -1) -> int:
         """direct_rl_env.py:390-407: seed torch / numpy / random (no replicator here)."""
@@ -301,14 +346,16 @@ class DirectRLEnv:
     # ------------------------------------------------------------------ subclass hooks
     def _reseed(self, seed: int):
         """Re-seed the device streams (subclasses extend it): here the Philox key of the noise models, of
-        the interval events (whose timers stay as they are: DirectRLEnv never resets the event manager) and of the
-        command terms."""
+        the interval events (whose timers stay as they are: DirectRLEnv never resets the event manager), of the
+        command terms and of the observation terms' noise."""
         if self._noise is not None:
             self._noise.seed = int(seed)
         if self._events is not None:
             self._events.seed = int(seed)
         if self._commands is not None:
             self._commands.seed = int(seed)
+        if self._observations is not None:
+            self._observations.seed = int(seed)
 
     def _reset_impl(self):
         raise NotImplementedError

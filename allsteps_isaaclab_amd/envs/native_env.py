@@ -99,6 +99,34 @@ class NativeDirectEnv(DirectRLEnv):
     def _commands_root_state(self):
         return self.state["root_quat"], self.state["root_lin"], self.state["root_ang"]
 
+    _actions_clamped = False  # the env's `actions` clamps the last action to [-1, 1] (the walker's)
+
+    def _observations_context(self):
+        from .observations import ObsContext
+
+        d = self.robot.data
+        hs = self.height_scanner
+        return ObsContext(
+            joint_names=list(d.joint_names),
+            default_joint_pos=d.default_joint_pos[0].detach().cpu().numpy(),
+            default_joint_vel=d.default_joint_vel[0].detach().cpu().numpy(),
+            soft_joint_pos_limits=d.soft_joint_pos_limits[0].detach().cpu().numpy(),
+            action_cols=int(self.cfg.action_space), clamp_actions=self._actions_clamped,
+            command_names=[] if self._commands is None else list(self._commands.terms.names),
+            ray_sensors={} if hs is None else {"height_scanner": int(hs.num_rays)},
+            imu_names=[] if self._imus is None else list(self._imus.sensors))
+
+    def _observations_sources(self) -> dict:
+        s, hs, im, cm = self.state, self.height_scanner, self._imus, self._commands
+        a = self._actions
+        if a.dtype != torch.float32 or not a.is_contiguous():
+            a = self._actions = a.float().contiguous()
+        return {"root_pos": s["root_pos"], "root_quat": s["root_quat"], "root_lin": s["root_lin"],
+                "root_ang": s["root_ang"], "q": s["q"], "qd": s["qd"], "actions": a,
+                "commands": None if cm is None or not len(cm.terms.names) else cm.vel,
+                "imu": None if im is None else im.data,
+                "ray_hits": None if hs is None else hs.hits, "ray_pose": None if hs is None else hs.pose}
+
     def _report_or_raise(self, what: str) -> _ContactReport:
         if self._report is None:
             raise _native.NativeError(
@@ -127,10 +155,12 @@ class NativeDirectEnv(DirectRLEnv):
         timestamp (contact_timers (4, B, N), contact_timestamp (N,)); with cfg.imu, the IMUs' previous world
         velocities (imu_prev_lin_vel, imu_prev_ang_vel, (3, S, N) each); with cfg.commands, the command streams'
         counter and the terms' state (command_t, command_time_left, command_vel_b, command_heading_target,
-        command_flags, command_counter, command_metrics, command_last_metrics)."""
+        command_flags, command_counter, command_metrics, command_last_metrics); with cfg.observations, the observation
+        streams' counters, the push counts and each group's output rows, which hold its history (observation_t,
+        observation_count, (groups, N) each; observation_history_<group>, (N, columns))."""
         tm, im = self._contact_timers, self._imus
         return {**{k: v.clone() for k, v in self.state.items()}, **self._noise_get_state(),
-                **self._events_get_state(), **self._commands_get_state(),
+                **self._events_get_state(), **self._commands_get_state(), **self._observations_get_state(),
                 **({} if tm is None else tm.get_state()),
                 **({} if im is None else im.get_state())}
 
@@ -141,6 +171,7 @@ class NativeDirectEnv(DirectRLEnv):
         if self._imus is not None:  # (and every env is outdated)
             self._imus.set_state(state)
         state = {k: v for k, v in state.items() if k not in _ContactTimers.STATE_KEYS + _ImuSet.STATE_KEYS}
+        state = self._observations_set_state(state)
         for k, v in self._commands_set_state(self._events_set_state(self._noise_set_state(state))).items():
             self.state[k].copy_(torch.as_tensor(v).to(self.state[k].device, self.state[k].dtype).reshape(
                 self.state[k].shape))

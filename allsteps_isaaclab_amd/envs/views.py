@@ -45,6 +45,40 @@ class _RobotData:
     root_ang_vel_w = property(lambda self: self._s["root_ang"].T)
     joint_pos = property(lambda self: self._s["q"][: self._nd].T)  # the state's rows past the model's hinges unused
     joint_vel = property(lambda self: self._s["qd"][: self._nd].T)
+    # the soft limits the env keeps (the quadruped's, by its soft_joint_pos_limit_factor), else the hard ones
+    soft_joint_pos_limits = property(lambda self: getattr(self._env, "soft_joint_pos_limits", self.joint_pos_limits))
+
+    # The base-frame quantities of articulation_data.py -- torch expressions over the views, the reference's
+    # quat_rotate_inverse / quat_apply (math.py:546-564, 606-625); the kernels compute the same from the same rows.
+    @staticmethod
+    def _rotate_inverse(q: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
+        q_w, q_vec = q[..., 0], q[..., 1:]
+        a = v * (2.0 * q_w**2 - 1.0).unsqueeze(-1)
+        b = torch.cross(q_vec, v, dim=-1) * q_w.unsqueeze(-1) * 2.0
+        c = q_vec * torch.bmm(q_vec.reshape(q.shape[0], 1, 3), v.reshape(q.shape[0], 3, 1)).squeeze(-1) * 2.0
+        return a - b + c
+
+    @property
+    def root_lin_vel_b(self) -> torch.Tensor:
+        return self._rotate_inverse(self.root_quat_w, self.root_lin_vel_w)
+
+    @property
+    def root_ang_vel_b(self) -> torch.Tensor:
+        return self._rotate_inverse(self.root_quat_w, self.root_ang_vel_w)
+
+    @property
+    def projected_gravity_b(self) -> torch.Tensor:
+        g = torch.tensor((0.0, 0.0, -1.0), device=self._s["root_quat"].device).repeat(self._s["root_quat"].shape[1], 1)
+        return self._rotate_inverse(self.root_quat_w, g)
+
+    @property
+    def heading_w(self) -> torch.Tensor:
+        q = self.root_quat_w
+        v = torch.tensor((1.0, 0.0, 0.0), device=q.device).repeat(q.shape[0], 1)
+        xyz = q[:, 1:]
+        t = xyz.cross(v, dim=-1) * 2
+        fwd = v + q[:, 0:1] * t + xyz.cross(t, dim=-1)
+        return torch.atan2(fwd[:, 1], fwd[:, 0])
 
     @property
     def joint_acc(self) -> torch.Tensor:

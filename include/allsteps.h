@@ -614,6 +614,66 @@ int as_commands_reset(const as_command_term_t* terms, int32_t num_terms, float* 
                       uint32_t* t, const uint8_t* mask, int32_t n, const float* draws, uint64_t seed,
                       int64_t env_id_offset, void* stream);
 
+/* Observation manager, off by default: the term groups of cfg.observations (isaaclab/managers/
+ * observation_manager.py, the term functions of isaaclab/envs/mdp/observations.py).  One launch assembles one
+ * group: per term the value from the env's device state, then noise, clip, scale and the history, written into the
+ * row-major out [n][out_cols] -- the terms side by side, each as `history` slots of `width` columns, oldest first.
+ * The caller launches it last in a step, after as_step, as_commands_step and as_events_interval, on the same stream
+ * (manager_based_rl_env.py step).  Stateless entry points over caller-owned device buffers -- no as_env_t.  The
+ * sources are field-major / env-minor ([rows][n]) except the actions ([n][action_cols]).  Formulas, rounding order,
+ * history rule and the Philox stream layout: csrc/allsteps_observations.h.  Both calls are graph-safe: the term
+ * descriptors, the column table and the output map are read from device memory at every launch. */
+#define AS_MAX_OBS_GROUPS 4
+#define AS_MAX_OBS_TERMS 16       /* terms of a group */
+#define AS_MAX_OBS_COLS 256       /* columns of a group before the history */
+#define AS_MAX_OBS_OUT_COLS 1280  /* columns of a group's output, history included */
+#define AS_OBS_COL_ROWS 6         /* column table rows: source row (int32) | a | b | noise p0 | noise p1 | scale */
+enum {
+  AS_OBS_GATHER = 0,         /* src[row] - a                          (a = 0, or the joint default) */
+  AS_OBS_LIMIT_NORM = 1,     /* 2 (src[row] - a) / b                  scale_transform: a the centre, b the range */
+  AS_OBS_QUAT_UNIQUE = 2,    /* src[row], negated where the quaternion's w < 0 */
+  AS_OBS_ROTATE_INVERSE = 3, /* quat_rotate_inverse(root_quat, src rows) -- src AS_OBS_SRC_GRAVITY: (0, 0, -1) */
+  AS_OBS_HEIGHT_SCAN = 4,    /* (ray_pose[2] - ray_hits[row]) - a     a the offset */
+  AS_OBS_LAST_ACTION = 5     /* actions[e][row], 0 for an env the step reset; flags & 1: clamped to [-1, 1] */
+};
+enum {
+  AS_OBS_SRC_ROOT_POS = 0, AS_OBS_SRC_ROOT_QUAT, AS_OBS_SRC_ROOT_LIN, AS_OBS_SRC_ROOT_ANG, AS_OBS_SRC_Q,
+  AS_OBS_SRC_QD, AS_OBS_SRC_COMMANDS, AS_OBS_SRC_IMU, AS_OBS_SRC_RAY_HITS, AS_OBS_SRC_RAY_POSE, AS_OBS_SRC_ACTIONS,
+  AS_OBS_SRC_GRAVITY, AS_OBS_NUM_SOURCES
+};
+typedef struct {
+  int32_t kind;               /* AS_OBS_* */
+  int32_t source;             /* AS_OBS_SRC_* */
+  int32_t width;              /* columns of the term before the history */
+  int32_t col;                /* its first column among the group's pre-history columns */
+  int32_t out_col;            /* its first column in the output */
+  int32_t history;            /* slots, >= 1 (history_length 0 and 1 are both one slot) */
+  int32_t noise_kind;         /* AS_NOISE_NONE / CONSTANT / UNIFORM / GAUSSIAN; parameters in the column table */
+  int32_t noise_op;           /* AS_NOISE_ADD / SCALE / ABS */
+  int32_t clip;               /* != 0: clip to [clip_lo, clip_hi] as torch's clip_ (a NaN stays a NaN) */
+  float clip_lo, clip_hi;
+  int32_t flags;              /* bit 0: AS_OBS_LAST_ACTION clamps to [-1, 1] (an env whose `actions` clamps) */
+} as_observation_term_t;
+typedef struct {
+  const float* ptr[AS_OBS_NUM_SOURCES]; /* device rows of each source, NULL: not there (reads as 0) */
+  int32_t rows[AS_OBS_NUM_SOURCES];     /* rows of each source ([rows][n]; the actions: action columns) */
+} as_observation_sources_t;
+/* One group, one launch.  terms [num_terms], cols [AS_OBS_COL_ROWS][AS_MAX_OBS_COLS] 32-bit words and omap
+ * [out_cols] int32 (pre-history column | last slot << 8 | term width << 9) are device memory.  An env with reset[e]
+ * | reset2[e] != 0 ([n] uint8 each, either may be NULL) has its push count set to 0 first and its last action read
+ * as 0; an env at push count 0 fills every slot with the new value (CircularBuffer.append).  Then count[e] += 1 and
+ * t[e] += 1.  draws: NULL (Philox at (seed, env_id_offset + e, t[e], group * 64 + column / 4, tag)) or [d0][n]
+ * injected draws (uniforms in [0, 1) or unit normals as the term's noise takes them). */
+int as_observations_step(const as_observation_term_t* terms, int32_t num_terms, const float* cols,
+                         const int32_t* omap, int32_t d0, int32_t out_cols, int32_t group,
+                         const as_observation_sources_t* sources, float* out, int32_t* count, uint32_t* t,
+                         const uint8_t* reset, const uint8_t* reset2, int32_t n, const float* draws, uint64_t seed,
+                         int64_t env_id_offset, void* stream);
+/* ObservationManager.reset(env_ids) of one group: for the envs with mask[e] != 0 ([n] uint8; NULL: every env) the
+ * push count becomes 0 and the output row 0 (CircularBuffer.reset).  Nothing is computed, t is not advanced. */
+int as_observations_reset(float* out, int32_t out_cols, int32_t* count, const uint8_t* mask, int32_t n,
+                          void* stream);
+
 /* The H^-1 sweep plan for a model (round 6, ABI 5; no device needed). The step kernel sweeps the
  * padded joint-space inertia last block first and, for the trees it is compiled for (the walker, the
  * C5 quadruped), skips the column quads in which the pivot rows are structurally zero -- an exact
