@@ -29,7 +29,7 @@ EXPORTED_SYMBOLS = [
     "as_contact_forces", "as_noise_actions", "as_noise_post", "as_events_init", "as_events_interval",
     "as_contact_timers", "as_ray_cast", "as_imu", "as_ray_camera",
     "as_frame_transformer", "as_commands_step", "as_commands_reset", "as_observations_step",
-    "as_observations_reset",
+    "as_observations_reset", "as_rewards_step", "as_rewards_reset",
 ]
 MAXB = 32  # AS_MAX_BODIES
 MAXC = 10  # AS_MAX_CONTACTS
@@ -256,6 +256,64 @@ def observations_reset(out, count, mask=None, stream=None):
           "as_observations_reset")
 
 
+MAX_REW_TERMS = 32  # AS_MAX_REW_TERMS
+MAX_REW_IDS = 32  # AS_MAX_REW_IDS: entries of a term's row of the index table
+REW_TABLE_ROWS = 3  # AS_REW_TABLE_ROWS: id (int32) | a | b
+REW_KINDS = ("is_alive", "is_terminated", "lin_vel_z_l2", "ang_vel_xy_l2", "flat_orientation_l2", "base_height_l2",
+             "joint_vel_l1", "joint_vel_l2", "joint_deviation_l1", "joint_pos_limits", "joint_acc_l2", "action_l2",
+             "action_rate_l2", "undesired_contacts", "contact_forces", "feet_air_time",
+             "feet_air_time_positive_biped", "track_lin_vel_xy_exp", "track_ang_vel_z_exp",
+             "track_ang_vel_z_world_exp", "track_lin_vel_xy_yaw_frame_exp")  # AS_REW_*, in order
+# as_reward_term_t as 8 32-bit words: kind (int32) | weight (float32) | num_ids, cmd_row (int32) | p0, p1 (float32)
+# | two reserved words
+REW_TERM_WORDS = 8
+
+
+class AsRewardSources(C.Structure):
+    """as_reward_sources_t (include/allsteps.h): the device rows the reward terms read."""
+    _fields_ = [(k, C.c_void_p) for k in ("root_pos", "root_quat", "root_lin", "root_ang", "q", "qd", "qd_prev",
+                                          "commands", "net", "timers", "actions", "terminated")] + \
+               [(k, C.c_int32) for k in ("joint_rows", "qd_prev_rows", "command_rows", "depth", "bodies",
+                                         "timer_bodies", "action_cols", "clamp_actions")] + [("sim_dt", C.c_float)]
+
+
+def make_reward_sources(tensors: dict, sim_dt: float, clamp_actions: bool = False) -> AsRewardSources:
+    """as_reward_sources_t over {name: tensor or None}: root_pos / root_quat / root_lin / root_ang / q / qd / qd_prev
+    / commands (rows, n), net (depth, bodies, 3, n), timers (4, bodies, n), actions (n, A), terminated (n,) uint8."""
+    S = AsRewardSources()
+    for name, _ in AsRewardSources._fields_[:12]:
+        t = tensors.get(name)
+        if t is not None:
+            setattr(S, name, t.data_ptr())
+    rows = lambda name, dim=0: 0 if tensors.get(name) is None else int(tensors[name].shape[dim])  # noqa: E731
+    S.joint_rows = min(rows("q"), rows("qd"))
+    S.qd_prev_rows, S.command_rows = rows("qd_prev"), rows("commands")
+    S.depth, S.bodies, S.timer_bodies = rows("net"), rows("net", 1), rows("timers", 1)
+    S.action_cols, S.clamp_actions, S.sim_dt = rows("actions", 1), int(bool(clamp_actions)), float(sim_dt)
+    return S
+
+
+def rewards_step(terms, table, kinds: int, sources: AsRewardSources, reward, episode_sums, step_reward,
+                 last_episode_sums=None, prev_actions=None, reset=None, reset2=None, dt: float = 0.0, stream=None):
+    """as_rewards_step: every term of cfg.rewards in one launch.  terms (num_terms, 8) float32 device rows of
+    as_reward_term_t, table (3, 32, 32) float32 words, kinds the bitmask of the kinds the descriptors hold; reward
+    (n,), episode_sums / step_reward / last_episode_sums (num_terms, n), prev_actions (n, A); reset / reset2 (n,)
+    uint8 / bool or None."""
+    check(load().as_rewards_step(terms.data_ptr(), terms.shape[0], table.data_ptr(), kinds, C.byref(sources),
+                                 reward.data_ptr(), episode_sums.data_ptr(), step_reward.data_ptr(),
+                                 _ptr(last_episode_sums), _ptr(prev_actions), _ptr(reset), _ptr(reset2),
+                                 reward.shape[0], dt, stream), "as_rewards_step")
+
+
+def rewards_reset(episode_sums, prev_actions=None, mask=None, stream=None):
+    """as_rewards_reset: the episodic sums (num_terms, n) and prev_actions (n, A) of the envs in mask ((n,) uint8 /
+    bool, None: all) become 0."""
+    k, n = episode_sums.shape
+    check(load().as_rewards_reset(episode_sums.data_ptr(), k, _ptr(prev_actions),
+                                  0 if prev_actions is None else prev_actions.shape[1], _ptr(mask), n, stream),
+          "as_rewards_reset")
+
+
 def unpack_report_ids(w):
     """(link, link2, stone, foot) of a record's ids word (int array or tensor); -1 = none."""
     return w & 0xFF, (w >> 8 & 0xFF) - 1, (w >> 16 & 0xFF) - 1, (w >> 24 & 0xFF) - 1
@@ -436,6 +494,8 @@ def load() -> C.CDLL:
     L.as_commands_reset.argtypes = [V, I32, V, V, V, V, V, V, V, V, V, I32, V, U64, I64, V]
     L.as_observations_step.argtypes = [V, I32, V, V, I32, I32, I32, V, V, V, V, V, V, I32, V, U64, I64, V]
     L.as_observations_reset.argtypes = [V, I32, V, V, I32, V]
+    L.as_rewards_step.argtypes = [V, I32, V, C.c_uint32, V, V, V, V, V, V, V, V, I32, C.c_float, V]
+    L.as_rewards_reset.argtypes = [V, I32, V, I32, V, I32, V]
     L.as_last_error.restype = C.c_char_p
     L.as_build_id.restype = C.c_char_p
     for name in EXPORTED_SYMBOLS:

@@ -1019,6 +1019,112 @@ int as_observations_reset(float* out, int32_t out_cols, int32_t* count, const ui
   return AS_OK;
 }
 
+int as_rewards_step(const as_reward_term_t* terms, int32_t num_terms, const float* table, uint32_t kinds,
+                    const as_reward_sources_t* sources, float* reward, float* episode_sums, float* step_reward,
+                    float* last_episode_sums, float* prev_actions, const uint8_t* reset, const uint8_t* reset2,
+                    int32_t n, float dt, void* stream) {
+  if (!terms || !table || !sources || !reward || !episode_sums || !step_reward)
+    return fail(AS_ERR_INVALID, "as_rewards_step: null argument (terms / table / sources / reward / episode_sums / "
+                                "step_reward)");
+  if (num_terms < 1 || num_terms > AS_MAX_REW_TERMS)
+    return fail(AS_ERR_INVALID, "as_rewards_step: num_terms " + std::to_string(num_terms) +
+                                    " outside [1, AS_MAX_REW_TERMS = " + std::to_string(AS_MAX_REW_TERMS) + "]");
+  if (n < 1 || n > AS_MAX_ENVS) return fail(AS_ERR_INVALID, "as_rewards_step: n outside [1, AS_MAX_ENVS]");
+  if (!std::isfinite(dt) || dt <= 0.0f) return fail(AS_ERR_INVALID, "as_rewards_step: dt is not finite or <= 0");
+  if (kinds >> AS_REW_NUM_KINDS) return fail(AS_ERR_INVALID, "as_rewards_step: kinds has bits of unknown kinds");
+  const as_reward_sources_t& S = *sources;
+  auto bit = [&](int k) { return ((kinds >> k) & 1u) != 0; };
+  auto missing = [&](int k, const char* what) {
+    return fail(AS_ERR_INVALID, std::string("as_rewards_step: a term of kind ") + std::to_string(k) +
+                                    " needs the source " + what + ", which is NULL or has no rows");
+  };
+  const bool root_state = S.root_quat && S.root_lin && S.root_ang;
+  const bool sim_dt = std::isfinite(S.sim_dt) && S.sim_dt > 0.0f;
+  const bool cmds = S.commands && S.command_rows >= 3;
+  const bool joints = S.q && S.qd && S.joint_rows >= 1;
+  const bool acts = S.actions && S.action_cols >= 1;
+  const bool net = S.net && S.depth >= 1 && S.bodies >= 1 && sim_dt;
+  const bool timers = S.timers && S.timer_bodies >= 1;
+  for (int k = 0; k < AS_REW_NUM_KINDS; ++k) {
+    if (!bit(k)) continue;
+    switch (k) {
+      case AS_REW_IS_ALIVE: case AS_REW_IS_TERMINATED:
+        if (!S.terminated) return missing(k, "terminated");
+        break;
+      case AS_REW_LIN_VEL_Z_L2: case AS_REW_ANG_VEL_XY_L2: case AS_REW_FLAT_ORIENTATION_L2:
+        if (!root_state) return missing(k, "root_quat / root_lin / root_ang");
+        break;
+      case AS_REW_BASE_HEIGHT_L2:
+        if (!S.root_pos) return missing(k, "root_pos");
+        break;
+      case AS_REW_JOINT_VEL_L1: case AS_REW_JOINT_VEL_L2: case AS_REW_JOINT_DEVIATION_L1:
+      case AS_REW_JOINT_POS_LIMITS:
+        if (!joints) return missing(k, "q / qd");
+        break;
+      case AS_REW_JOINT_ACC_L2:
+        if (!joints || !S.qd_prev || S.qd_prev_rows < 1 || !sim_dt) return missing(k, "qd_prev (and sim_dt)");
+        break;
+      case AS_REW_ACTION_L2:
+        if (!acts) return missing(k, "actions");
+        break;
+      case AS_REW_ACTION_RATE_L2:
+        if (!acts || !prev_actions) return missing(k, "actions / prev_actions");
+        break;
+      case AS_REW_UNDESIRED_CONTACTS: case AS_REW_CONTACT_FORCES:
+        if (!net) return missing(k, "net (and sim_dt)");
+        break;
+      case AS_REW_FEET_AIR_TIME: case AS_REW_FEET_AIR_TIME_BIPED:
+        if (!timers || !cmds) return missing(k, "timers / commands");
+        break;
+      case AS_REW_TRACK_LIN_VEL_XY_EXP: case AS_REW_TRACK_ANG_VEL_Z_EXP: case AS_REW_TRACK_LIN_VEL_XY_YAW_EXP:
+        if (!root_state || !cmds) return missing(k, "root state / commands");
+        break;
+      case AS_REW_TRACK_ANG_VEL_Z_WORLD_EXP:
+        if (!S.root_ang || !cmds) return missing(k, "root_ang / commands");
+        break;
+    }
+  }
+  if (prev_actions && !acts)
+    return fail(AS_ERR_INVALID, "as_rewards_step: prev_actions without actions (NULL, or no columns)");
+  if (S.joint_rows < 0 || S.qd_prev_rows < 0 || S.command_rows < 0 || S.depth < 0 || S.bodies < 0 ||
+      S.timer_bodies < 0 || S.action_cols < 0 || (prev_actions && S.actions && S.action_cols < 1))
+    return fail(AS_ERR_INVALID, "as_rewards_step: a negative row count, or actions without columns");
+  as::RewardsArgs a{};
+  a.terms = terms;
+  a.table = table;
+  a.num_terms = num_terms;
+  a.n = n;
+  a.src = S;
+  a.reward = reward;
+  a.episode_sums = episode_sums;
+  a.step_reward = step_reward;
+  a.last_episode_sums = last_episode_sums;
+  a.prev_actions = prev_actions;
+  a.reset = reset;
+  a.reset2 = reset2;
+  a.dt = dt;
+  HIP_TRY(as::launch_rewards_step(a, reinterpret_cast<hipStream_t>(stream)));
+  return AS_OK;
+}
+
+int as_rewards_reset(float* episode_sums, int32_t num_terms, float* prev_actions, int32_t action_cols,
+                     const uint8_t* mask, int32_t n, void* stream) {
+  if (!episode_sums) return fail(AS_ERR_INVALID, "as_rewards_reset: null argument (episode_sums)");
+  if (num_terms < 1 || num_terms > AS_MAX_REW_TERMS)
+    return fail(AS_ERR_INVALID, "as_rewards_reset: num_terms outside [1, AS_MAX_REW_TERMS]");
+  if (prev_actions && action_cols < 1) return fail(AS_ERR_INVALID, "as_rewards_reset: prev_actions without columns");
+  if (n < 1 || n > AS_MAX_ENVS) return fail(AS_ERR_INVALID, "as_rewards_reset: n outside [1, AS_MAX_ENVS]");
+  as::RewardsArgs a{};
+  a.episode_sums = episode_sums;
+  a.num_terms = num_terms;
+  a.prev_actions = prev_actions;
+  a.src.action_cols = action_cols;
+  a.reset = mask;
+  a.n = n;
+  HIP_TRY(as::launch_rewards_reset(a, reinterpret_cast<hipStream_t>(stream)));
+  return AS_OK;
+}
+
 int as_set_graph_safe(as_env_t* env, int32_t on) {
   if (!env) return fail(AS_ERR_INVALID, "as_set_graph_safe: null handle");
   env->graph_safe = on != 0;

@@ -246,6 +246,24 @@ struct ObservationsArgs {
   int64_t env_offset;
 };
 
+// k_rewards_step / k_rewards_reset (as_rewards_step / as_rewards_reset, reward_kernels.h): the terms of cfg.rewards.
+// k_rewards_reset reads episode_sums, num_terms, prev_actions, src.action_cols, n and `reset` as its mask (null:
+// every env) only
+struct RewardsArgs {
+  const as_reward_term_t* terms;  // [num_terms] device memory
+  const float* table;             // [AS_REW_TABLE_ROWS][AS_MAX_REW_TERMS][AS_MAX_REW_IDS] 32-bit words, device memory
+  int32_t num_terms, n;
+  as_reward_sources_t src;
+  float* reward;                  // [n]
+  float* episode_sums;            // [num_terms][n]
+  float* step_reward;             // [num_terms][n]
+  float* last_episode_sums;       // [num_terms][n] or null: not written
+  float* prev_actions;            // [n][action_cols] or null: not written, reads as 0
+  const uint8_t* reset;           // [n] or null
+  const uint8_t* reset2;          // [n] a second mask, ORed with the first, or null
+  float dt;
+};
+
 // k_commands_step / k_commands_reset (as_commands_step / as_commands_reset, command_kernels.h): every buffer
 // field-major / env-minor.  k_commands_reset reads no root state, no dt and `reset` as its mask (null: every env)
 struct CommandsArgs {
@@ -338,6 +356,8 @@ hipError_t launch_commands_step(const CommandsArgs& a, hipStream_t stream);
 hipError_t launch_commands_reset(const CommandsArgs& a, hipStream_t stream);
 hipError_t launch_observations(const ObservationsArgs& a, hipStream_t stream);
 hipError_t launch_observations_reset(const ObservationsArgs& a, hipStream_t stream);
+hipError_t launch_rewards_step(const RewardsArgs& a, hipStream_t stream);
+hipError_t launch_rewards_reset(const RewardsArgs& a, hipStream_t stream);
 hipError_t launch_events_interval(const EventsArgs& a, hipStream_t stream);
 hipError_t launch_events_init(const EventsArgs& a, hipStream_t stream);
 hipError_t launch_noise_actions(const NoiseActArgs& a, hipStream_t stream);

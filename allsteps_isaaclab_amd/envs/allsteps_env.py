@@ -74,6 +74,7 @@ class AllstepsEnv(NativeDirectEnv):
         self.left_body_indices = L(cfg.left_body_names)
         self.negation_body_indices = L(cfg.negation_body_names)
         self._observations_start()
+        self._rewards_start()
 
     _actions_clamped = True  # `actions` below
 

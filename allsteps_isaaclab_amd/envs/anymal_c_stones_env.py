@@ -77,6 +77,7 @@ class AnymalCStonesEnv(NativeDirectEnv):
         self.robot = _RobotView(self, default_joint_pos=self.default_joint_pos)
         self._actions = torch.zeros(n, self.num_dof, dtype=torch.float32, device=dev)
         self._observations_start()
+        self._rewards_start()
 
     @property
     def actions(self) -> torch.Tensor:

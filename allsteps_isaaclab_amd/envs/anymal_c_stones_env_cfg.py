@@ -115,6 +115,13 @@ class AnymalCStonesEnvCfg:
     # env.observation_manager and under its name in the returned observation dict; "policy" stays the task's own.
     # Anything not served raises at construction.  None: nothing is allocated or launched.
     observations: object = None
+    # Reward manager (the reference's ManagerBasedRLEnvCfg `rewards`): a dict or cfg object whose entries are
+    # utils.rewards RewardTermCfg terms (None entries are skipped), or None.  The weighted sum, the episodic sums and
+    # the per-step term values are computed on the device by k_rewards_step (csrc/reward_kernels.h), one launch per
+    # step, as env.reward_manager.  step() returns the task's own reward unless rewards_replace_task_reward, which
+    # makes it the manager's.  Anything not served raises at construction.  None: nothing is allocated or launched.
+    rewards: object = None
+    rewards_replace_task_reward: bool = False
 
     # the stepping-stone task (authored; include/allsteps.h as_quad_task_t): the ALLSTEPS target
     # machine and reward terms (allsteps_env.py:347-394, 418-457) on four feet

@@ -43,6 +43,9 @@ class DirectRLEnv:
     # cfg.observations (the reference's ObservationManager): the device state of the observation kernel, built by
     # _observations_start once the subclass has its views.  None: step() launches nothing for it.
     _observations = None
+    # cfg.rewards (the reference's RewardManager): the device state of the reward kernel, built by _rewards_start
+    # once the subclass has its views.  None: step() launches nothing for it.
+    _rewards = None
 
     def __init__(self, cfg, render_mode: str | None = None, **kwargs):
         self.cfg = cfg
@@ -153,7 +156,10 @@ class DirectRLEnv:
         cfg.observations: the term groups are assembled last, one launch per group, after the sensors their terms
         read were brought up to date (manager_based_rl_env.py step: the observations follow the reset, the commands
         and the interval events); they join the returned observation dict under their group names and write only
-        their own buffers."""
+        their own buffers.  With cfg.rewards: the reward terms are computed in one launch after the sensors, the
+        commands and the events and before the observation manager, on the state as the step left it (an env the
+        step reset shows its post-reset state); the task's own reward is returned unless
+        cfg.rewards_replace_task_reward."""
         action = action.to(self._device)
         self._sim_step_counter += self.cfg.decimation
         nz = self._noise
@@ -173,6 +179,10 @@ class DirectRLEnv:
             self._events.apply(*self._events_root_velocity(), self._noise_offset(), self._noise_stream())
         if nz is not None:
             nz.post(out[0]["policy"], out[2], out[3], self._noise_offset(), self._noise_stream())
+        if self._rewards is not None:
+            rew = self._rewards.compute(self.step_dt, out[2], out[2], out[3])
+            if self._rewards.replace_task_reward:
+                out = (out[0], rew, *out[2:])
         if self._observations is not None:
             out[0].update(self._observations.compute(out[2], out[3]))
         self.common_step_counter += 1
@@ -235,6 +245,8 @@ class DirectRLEnv:
             self._commands.reset(mask, self._noise_offset(), self._noise_stream())
         if self._observations is not None:  # ObservationManager.reset(env_ids): the histories, no compute
             self._observations.reset(mask)
+        if self._rewards is not None:  # RewardManager.reset(env_ids): the episodic sums and prev_actions
+            self._rewards.reset(mask)
 
     # ------------------------------------------------------------------ interval events
     def _events_root_velocity(self):
@@ -307,6 +319,38 @@ class DirectRLEnv:
         if self._observations is not None:
             self._observations.set_state(state)
         return {k: v for k, v in state.items() if not EnvObservations.is_state_key(k)}
+
+    # ------------------------------------------------------------------ reward manager
+    def _rewards_start(self) -> None:
+        """Build the reward manager of cfg.rewards once the subclass has its state, views and sensors (its
+        constructor calls it beside _observations_start); raises NativeError for a cfg the kernel does not serve."""
+        from .rewards import EnvRewards, RewardManagerView
+
+        if EnvRewards.wanted(self.cfg):
+            self._rewards = EnvRewards(self.cfg, self, self.num_envs, self._device)
+            self.reward_manager = RewardManagerView(self._rewards)
+
+    def _rewards_context(self):
+        """The RewContext of the env: what its terms can read (subclass hook)."""
+        raise NotImplementedError(f"{type(self).__name__} does not serve cfg.rewards")
+
+    def _rewards_sources(self, net: bool = False) -> dict:
+        """{source name: device tensor} of the rows the terms read; net: the contact report's dense net impulses
+        are wanted, brought up to date (subclass hook)."""
+        raise NotImplementedError(f"{type(self).__name__} does not serve cfg.rewards")
+
+    def _rewards_get_state(self) -> dict:
+        """The episodic sums, the step's term values, the last episode's sums and the previous actions (no keys
+        without cfg.rewards)."""
+        return {} if self._rewards is None else self._rewards.get_state()
+
+    def _rewards_set_state(self, state: dict) -> dict:
+        """Load the reward keys of a set_state dict; returns the dict without them."""
+        from .rewards import EnvRewards
+
+        if self._rewards is not None:
+            self._rewards.set_state(state)
+        return {k: v for k, v in state.items() if not EnvRewards.is_state_key(k)}
 
     @staticmethod
     def seed(seed: int = -1) -> int:

@@ -9,7 +9,8 @@ import torch
 from .. import _native
 from .direct_rl_env import DirectRLEnv
 from .state import alloc_state
-from .views import _ContactReport, _ContactTimers, _FrameTransformerSet, _ImuSet, _RayCaster, _RayCasterCamera
+from .views import (_ContactReport, _ContactTimers, _FootSensor, _FrameTransformerSet, _ImuSet, _RayCaster,
+                    _RayCasterCamera)
 
 
 class NativeDirectEnv(DirectRLEnv):
@@ -127,6 +128,37 @@ class NativeDirectEnv(DirectRLEnv):
                 "imu": None if im is None else im.data,
                 "ray_hits": None if hs is None else hs.hits, "ray_pose": None if hs is None else hs.pose}
 
+    def _rewards_context(self):
+        from .rewards import RewContext, SensorInfo
+
+        d = self.robot.data
+        rep, tm = self._report, self._contact_timers
+        sensors = {}
+        for name, s in vars(self).items():  # the env's foot sensors, under their attribute names
+            if isinstance(s, _FootSensor):
+                sensors[name] = SensorInfo(list(s.body_names),
+                                           [0 if rep is None else rep.foot_body[f] for f in s._feet], list(s._feet))
+        return RewContext(
+            joint_names=list(d.joint_names),
+            default_joint_pos=d.default_joint_pos[0].detach().cpu().numpy(),
+            soft_joint_pos_limits=d.soft_joint_pos_limits[0].detach().cpu().numpy(),
+            action_cols=int(self.cfg.action_space), step_dt=self.step_dt,
+            command_names=[] if self._commands is None else list(self._commands.terms.names),
+            sensors=sensors, contact_forces=rep is not None, contact_air_time=tm is not None)
+
+    def _rewards_sources(self, net: bool = False) -> dict:
+        s, cm, rep, tm = self.state, self._commands, self._report, self._contact_timers
+        a = self._actions
+        if a.dtype != torch.float32 or not a.is_contiguous():
+            a = self._actions = a.float().contiguous()
+        nd = int(self.model["num_hinges"])
+        return {"root_pos": s["root_pos"], "root_quat": s["root_quat"], "root_lin": s["root_lin"],
+                "root_ang": s["root_ang"], "q": s["q"][:nd], "qd": s["qd"][:nd], "actions": a,
+                "qd_prev": None if rep is None else rep.qd_prev[:nd],
+                "commands": None if cm is None or not len(cm.terms.names) else cm.vel.view(-1, self.num_envs),
+                "net": rep.forces()[1] if (net and rep is not None) else None,
+                "timers": None if tm is None else tm.timers}
+
     def _report_or_raise(self, what: str) -> _ContactReport:
         if self._report is None:
             raise _native.NativeError(
@@ -157,10 +189,13 @@ class NativeDirectEnv(DirectRLEnv):
         counter and the terms' state (command_t, command_time_left, command_vel_b, command_heading_target,
         command_flags, command_counter, command_metrics, command_last_metrics); with cfg.observations, the observation
         streams' counters, the push counts and each group's output rows, which hold its history (observation_t,
-        observation_count, (groups, N) each; observation_history_<group>, (N, columns))."""
+        observation_count, (groups, N) each; observation_history_<group>, (N, columns)); with cfg.rewards, the
+        reward manager's episodic sums, step values and last episode's sums ((terms, N) each) and its previous
+        actions (reward_episode_sums, reward_step, reward_last_episode_sums, reward_prev_actions)."""
         tm, im = self._contact_timers, self._imus
         return {**{k: v.clone() for k, v in self.state.items()}, **self._noise_get_state(),
                 **self._events_get_state(), **self._commands_get_state(), **self._observations_get_state(),
+                **self._rewards_get_state(),
                 **({} if tm is None else tm.get_state()),
                 **({} if im is None else im.get_state())}
 
@@ -171,7 +206,7 @@ class NativeDirectEnv(DirectRLEnv):
         if self._imus is not None:  # (and every env is outdated)
             self._imus.set_state(state)
         state = {k: v for k, v in state.items() if k not in _ContactTimers.STATE_KEYS + _ImuSet.STATE_KEYS}
-        state = self._observations_set_state(state)
+        state = self._rewards_set_state(self._observations_set_state(state))
         for k, v in self._commands_set_state(self._events_set_state(self._noise_set_state(state))).items():
             self.state[k].copy_(torch.as_tensor(v).to(self.state[k].device, self.state[k].dtype).reshape(
                 self.state[k].shape))

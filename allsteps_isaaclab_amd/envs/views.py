@@ -857,3 +857,13 @@ class _RobotView:
         s["q"][:, ids] = position.T.float()
         s["qd"][:, ids] = velocity.T.float()
         self._env._scene_changed()
+
+
+def __getattr__(name: str):
+    """``RewardManagerView`` (``env.reward_manager``, the view of cfg.rewards' device state) lives in envs/rewards.py
+    and is loaded on first use, so the default path never imports it."""
+    if name == "RewardManagerView":
+        from .rewards import RewardManagerView
+
+        return RewardManagerView
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -674,6 +674,86 @@ int as_observations_step(const as_observation_term_t* terms, int32_t num_terms, 
 int as_observations_reset(float* out, int32_t out_cols, int32_t* count, const uint8_t* mask, int32_t n,
                           void* stream);
 
+/* Reward manager, off by default: the weighted term sums of cfg.rewards (isaaclab/managers/reward_manager.py, the
+ * term functions of isaaclab/envs/mdp/rewards.py and of the velocity task's mdp/rewards.py).  One launch computes
+ * every term of every env: per term in cfg order value = (f weight) dt, reward += value, episode_sums[k] += value,
+ * step_reward[k] = value / dt; a term whose weight is exactly 0 is skipped (f is not evaluated, its rows keep their
+ * values).  Then, for an env with reset[e] | reset2[e] != 0: last_episode_sums = episode_sums, episode_sums = 0,
+ * prev_actions = 0; for every other env prev_actions = actions.  The caller launches it after as_step (and the
+ * contact forces, timers and commands its terms read) on the same stream; the state rows of an env the step reset
+ * are the post-reset ones.  Stateless entry points over caller-owned device buffers -- no as_env_t.  Every buffer is
+ * field-major / env-minor ([rows][n]) except actions and prev_actions ([n][action_cols]).  Formulas and the float32
+ * rounding order: csrc/allsteps_rewards.h.  Both calls are graph-safe: the term descriptors and the index table are
+ * read from device memory at every launch.  Symbols added only: AS_ABI_VERSION stays 6. */
+#define AS_MAX_REW_TERMS 32
+#define AS_MAX_REW_IDS 32   /* entries of a term's row of the index table (joints or bodies) */
+#define AS_REW_TABLE_ROWS 3 /* table [3][AS_MAX_REW_TERMS][AS_MAX_REW_IDS] words: id (int32) | a | b */
+enum {
+  AS_REW_IS_ALIVE = 0,          /* 1 - terminated */
+  AS_REW_IS_TERMINATED,         /* terminated */
+  AS_REW_LIN_VEL_Z_L2,          /* root_lin_vel_b[2]^2 */
+  AS_REW_ANG_VEL_XY_L2,         /* root_ang_vel_b[0]^2 + [1]^2 */
+  AS_REW_FLAT_ORIENTATION_L2,   /* projected_gravity_b[0]^2 + [1]^2 */
+  AS_REW_BASE_HEIGHT_L2,        /* (root_pos[2] - p0)^2                          p0 target_height */
+  AS_REW_JOINT_VEL_L1,          /* sum |qd[id]| */
+  AS_REW_JOINT_VEL_L2,          /* sum qd[id]^2 */
+  AS_REW_JOINT_DEVIATION_L1,    /* sum |q[id] - a|                               a the default pose */
+  AS_REW_JOINT_POS_LIMITS,      /* sum -min(q[id] - a, 0) + max(q[id] - b, 0)    a, b the soft limits */
+  AS_REW_JOINT_ACC_L2,          /* sum ((qd[id] - qd_prev[id]) / sim_dt)^2 */
+  AS_REW_ACTION_L2,             /* sum action^2 */
+  AS_REW_ACTION_RATE_L2,        /* sum (action - prev_action)^2 */
+  AS_REW_UNDESIRED_CONTACTS,    /* count of bodies whose max-over-slots |net / sim_dt| > p0 */
+  AS_REW_CONTACT_FORCES,        /* sum max(that maximum - p0, 0) */
+  AS_REW_FEET_AIR_TIME,         /* sum (last_air - p0) first_contact, gated; p1 = float32(step_dt + 1e-8) */
+  AS_REW_FEET_AIR_TIME_BIPED,   /* feet_air_time_positive_biped, threshold p0, gated */
+  AS_REW_TRACK_LIN_VEL_XY_EXP,  /* exp(-|cmd_xy - root_lin_vel_b_xy|^2 / p0)     p0 = float32(std^2) */
+  AS_REW_TRACK_ANG_VEL_Z_EXP,   /* exp(-(cmd_yaw - root_ang_vel_b[2])^2 / p0) */
+  AS_REW_TRACK_ANG_VEL_Z_WORLD_EXP, /* exp(-(cmd_yaw - root_ang[2])^2 / p0) */
+  AS_REW_TRACK_LIN_VEL_XY_YAW_EXP,  /* exp(-|cmd_xy - quat_rotate_inverse(yaw_quat(root_quat), root_lin)_xy|^2 / p0) */
+  AS_REW_NUM_KINDS
+};
+typedef struct {
+  int32_t kind;     /* AS_REW_* */
+  float weight;     /* float32(cfg weight); exactly 0: the term is skipped */
+  int32_t num_ids;  /* entries of the term's index-table row, <= AS_MAX_REW_IDS */
+  int32_t cmd_row;  /* first row of the term's command in `commands` (3 x the command term's index) */
+  float p0, p1;     /* the kind's constants, formed by the host as float32 the way torch takes a Python scalar */
+  int32_t reserved0, reserved1;
+} as_reward_term_t;
+typedef struct {
+  const float* root_pos;      /* [3][n] */
+  const float* root_quat;     /* [4][n] (w x y z) */
+  const float* root_lin;      /* [3][n] */
+  const float* root_ang;      /* [3][n] */
+  const float* q;             /* [joint_rows][n] */
+  const float* qd;            /* [joint_rows][n] */
+  const float* qd_prev;       /* [qd_prev_rows][n] the contact report's, or NULL */
+  const float* commands;      /* [command_rows][n] the command manager's vel rows, or NULL */
+  const float* net;           /* [depth][bodies][3][n] as_contact_forces' net impulses, or NULL */
+  const float* timers;        /* [4][timer_bodies][n] as_contact_timers' rows, or NULL */
+  const float* actions;       /* [n][action_cols], or NULL */
+  const uint8_t* terminated;  /* [n] the step's terminated flags, or NULL (reads as 0) */
+  int32_t joint_rows, qd_prev_rows, command_rows, depth, bodies, timer_bodies, action_cols;
+  int32_t clamp_actions;      /* != 0: an action is read clamped to [-1, 1] (an env whose `actions` clamps) */
+  float sim_dt;               /* the physics step: impulses / sim_dt are forces, (qd - qd_prev) / sim_dt joint_acc */
+} as_reward_sources_t;
+/* terms [num_terms] and table [AS_REW_TABLE_ROWS][AS_MAX_REW_TERMS][AS_MAX_REW_IDS] are device memory.  kinds: bit k
+ * set for every AS_REW_* kind a descriptor may hold (the host's knowledge of the device descriptors): a set bit whose
+ * source pointer is NULL is AS_ERR_INVALID, as are NULL terms / table / sources / reward / episode_sums /
+ * step_reward, num_terms outside [1, AS_MAX_REW_TERMS], a dt that is not finite or <= 0, prev_actions without
+ * actions -- all before any device call.  A source that is NULL, or an id outside its rows, reads as 0 on the
+ * device.  reward [n], episode_sums, step_reward and last_episode_sums [num_terms][n]; prev_actions
+ * [n][action_cols].  last_episode_sums and prev_actions may be NULL (not written) unless an AS_REW_ACTION_RATE_L2
+ * term needs the latter. */
+int as_rewards_step(const as_reward_term_t* terms, int32_t num_terms, const float* table, uint32_t kinds,
+                    const as_reward_sources_t* sources, float* reward, float* episode_sums, float* step_reward,
+                    float* last_episode_sums, float* prev_actions, const uint8_t* reset, const uint8_t* reset2,
+                    int32_t n, float dt, void* stream);
+/* RewardManager.reset(env_ids): for the envs with mask[e] != 0 ([n] uint8; NULL: every env) the episodic sums and
+ * prev_actions (may be NULL) become 0; step_reward and the reward are left alone, as in the reference. */
+int as_rewards_reset(float* episode_sums, int32_t num_terms, float* prev_actions, int32_t action_cols,
+                     const uint8_t* mask, int32_t n, void* stream);
+
 /* The H^-1 sweep plan for a model (round 6, ABI 5; no device needed). The step kernel sweeps the
  * padded joint-space inertia last block first and, for the trees it is compiled for (the walker, the
  * C5 quadruped), skips the column quads in which the pivot rows are structurally zero -- an exact
