@@ -29,7 +29,7 @@ EXPORTED_SYMBOLS = [
     "as_contact_forces", "as_noise_actions", "as_noise_post", "as_events_init", "as_events_interval",
     "as_contact_timers", "as_ray_cast", "as_imu", "as_ray_camera",
     "as_frame_transformer", "as_commands_step", "as_commands_reset", "as_observations_step",
-    "as_observations_reset", "as_rewards_step", "as_rewards_reset",
+    "as_observations_reset", "as_rewards_step", "as_rewards_reset", "as_terminations_step",
 ]
 MAXB = 32  # AS_MAX_BODIES
 MAXC = 10  # AS_MAX_CONTACTS
@@ -314,6 +314,54 @@ def rewards_reset(episode_sums, prev_actions=None, mask=None, stream=None):
           "as_rewards_reset")
 
 
+MAX_TERMINATION_TERMS = 16  # AS_MAX_TERMINATION_TERMS
+MAX_TERMINATION_IDS = 32  # AS_MAX_TERMINATION_IDS: entries of a term's row of the index table
+TERMINATION_TABLE_ROWS = 3  # AS_TERMINATION_TABLE_ROWS: id (int32) | a | b
+TERMINATION_KINDS = ("time_out", "command_resample", "bad_orientation", "root_height_below_minimum",
+                     "joint_pos_out_of_limit", "joint_pos_out_of_manual_limit", "joint_vel_out_of_manual_limit",
+                     "illegal_contact")  # AS_TERMINATION_*, in order
+# as_termination_term_t as 8 32-bit words: kind, time_out, num_ids, row (int32) | p0, p1 (float32) | i0 (int32) | one
+# reserved word
+TERMINATION_TERM_WORDS = 8
+
+
+class AsTerminationSources(C.Structure):
+    """as_termination_sources_t (include/allsteps.h): the device rows the termination terms read."""
+    _fields_ = [(k, C.c_void_p) for k in ("root_pos", "root_quat", "q", "qd", "time_left", "command_counter", "net",
+                                          "ep_len", "step_terminated", "step_truncated")] + \
+               [(k, C.c_int32) for k in ("joint_rows", "command_terms", "depth", "bodies")] + [("sim_dt", C.c_float)]
+
+
+def make_termination_sources(tensors: dict, sim_dt: float) -> AsTerminationSources:
+    """as_termination_sources_t over {name: tensor or None}: root_pos / root_quat / q / qd (rows, n), time_left
+    (terms, n) float32 and command_counter (terms, n) int32, net (depth, bodies, 3, n), ep_len (n,) int32,
+    step_terminated / step_truncated (n,) uint8."""
+    S = AsTerminationSources()
+    for name, _ in AsTerminationSources._fields_[:10]:
+        t = tensors.get(name)
+        if t is not None:
+            setattr(S, name, t.data_ptr())
+    rows = lambda name, dim=0: 0 if tensors.get(name) is None else int(tensors[name].shape[dim])  # noqa: E731
+    # one row count serves a pair of sources: that of whichever is there, the smaller where both are (a source that
+    # is not there is NULL and reads as 0)
+    both = lambda a, b: min([r for r in (rows(a), rows(b)) if r] or [0])  # noqa: E731
+    S.joint_rows = both("q", "qd")
+    S.command_terms = both("time_left", "command_counter")
+    S.depth, S.bodies, S.sim_dt = rows("net"), rows("net", 1), float(sim_dt)
+    return S
+
+
+def terminations_step(terms, table, kinds: int, sources: AsTerminationSources, term_dones, time_outs, terminated,
+                      dones, last_episode_dones=None, reset_request=None, stream=None):
+    """as_terminations_step: every term of cfg.terminations in one launch.  terms (num_terms, 8) float32 device rows
+    of as_termination_term_t, table (3, 16, 32) float32 words, kinds the bitmask of the kinds the descriptors hold;
+    term_dones / last_episode_dones (num_terms, n), time_outs / terminated / dones / reset_request (n,), all uint8."""
+    check(load().as_terminations_step(terms.data_ptr(), terms.shape[0], table.data_ptr(), kinds, C.byref(sources),
+                                      term_dones.data_ptr(), time_outs.data_ptr(), terminated.data_ptr(),
+                                      dones.data_ptr(), _ptr(last_episode_dones), _ptr(reset_request),
+                                      dones.shape[0], stream), "as_terminations_step")
+
+
 def unpack_report_ids(w):
     """(link, link2, stone, foot) of a record's ids word (int array or tensor); -1 = none."""
     return w & 0xFF, (w >> 8 & 0xFF) - 1, (w >> 16 & 0xFF) - 1, (w >> 24 & 0xFF) - 1
@@ -496,6 +544,7 @@ def load() -> C.CDLL:
     L.as_observations_reset.argtypes = [V, I32, V, V, I32, V]
     L.as_rewards_step.argtypes = [V, I32, V, C.c_uint32, V, V, V, V, V, V, V, V, I32, C.c_float, V]
     L.as_rewards_reset.argtypes = [V, I32, V, I32, V, I32, V]
+    L.as_terminations_step.argtypes = [V, I32, V, C.c_uint32, V, V, V, V, V, V, V, I32, V]
     L.as_last_error.restype = C.c_char_p
     L.as_build_id.restype = C.c_char_p
     for name in EXPORTED_SYMBOLS:

@@ -1,8 +1,9 @@
 """Shim of ``isaaclab.envs.mdp``: the event function the device event kernel serves, the height-scan
 observation over the device ray caster, the image observation over the device ray-cast camera, the IMU
 observations over the device IMU kernel, the velocity command cfgs and ``generated_commands`` over the device
-command kernel, the observation functions the device observation kernel serves, and the reward functions the device
-reward kernel serves (those of the velocity task's ``mdp`` among them)."""
+command kernel, the observation functions the device observation kernel serves, the reward functions the device
+reward kernel serves (those of the velocity task's ``mdp`` among them), and the termination functions the device
+termination kernel serves."""
 
 from allsteps_isaaclab_amd.utils.commands import (  # noqa: F401
     NormalVelocityCommandCfg, NullCommandCfg, UniformVelocityCommandCfg, generated_commands)
@@ -17,6 +18,10 @@ from allsteps_isaaclab_amd.utils.rewards import (  # noqa: F401
     joint_pos_limits, joint_vel_limits, applied_torque_limits, action_rate_l2, action_l2, undesired_contacts,
     contact_forces, track_lin_vel_xy_exp, track_ang_vel_z_exp, feet_air_time, feet_air_time_positive_biped,
     feet_slide, track_lin_vel_xy_yaw_frame_exp, track_ang_vel_z_world_exp)
+from allsteps_isaaclab_amd.utils.terminations import (  # noqa: F401
+    time_out, command_resample, bad_orientation, root_height_below_minimum, joint_pos_out_of_limit,
+    joint_pos_out_of_manual_limit, joint_vel_out_of_limit, joint_vel_out_of_manual_limit, joint_effort_out_of_limit,
+    illegal_contact)
 from allsteps_isaaclab_amd.utils.sensors import (  # noqa: F401
     height_scan, image, imu_ang_vel, imu_lin_acc, imu_orientation)
 
@@ -30,4 +35,7 @@ __all__ = ["push_by_setting_velocity", "height_scan", "image", "imu_orientation"
            "joint_vel_l2", "joint_acc_l2", "joint_deviation_l1", "joint_pos_limits", "joint_vel_limits",
            "applied_torque_limits", "action_rate_l2", "action_l2", "undesired_contacts", "contact_forces",
            "track_lin_vel_xy_exp", "track_ang_vel_z_exp", "feet_air_time", "feet_air_time_positive_biped",
-           "feet_slide", "track_lin_vel_xy_yaw_frame_exp", "track_ang_vel_z_world_exp"]
+           "feet_slide", "track_lin_vel_xy_yaw_frame_exp", "track_ang_vel_z_world_exp",
+           "time_out", "command_resample", "bad_orientation", "root_height_below_minimum", "joint_pos_out_of_limit",
+           "joint_pos_out_of_manual_limit", "joint_vel_out_of_limit", "joint_vel_out_of_manual_limit",
+           "joint_effort_out_of_limit", "illegal_contact"]

@@ -1125,6 +1125,71 @@ int as_rewards_reset(float* episode_sums, int32_t num_terms, float* prev_actions
   return AS_OK;
 }
 
+int as_terminations_step(const as_termination_term_t* terms, int32_t num_terms, const float* table, uint32_t kinds,
+                         const as_termination_sources_t* sources, uint8_t* term_dones, uint8_t* time_outs,
+                         uint8_t* terminated, uint8_t* dones, uint8_t* last_episode_dones, uint8_t* reset_request,
+                         int32_t n, void* stream) {
+  if (!terms || !table || !sources || !term_dones || !time_outs || !terminated || !dones)
+    return fail(AS_ERR_INVALID, "as_terminations_step: null argument (terms / table / sources / term_dones / "
+                                "time_outs / terminated / dones)");
+  if (num_terms < 1 || num_terms > AS_MAX_TERMINATION_TERMS)
+    return fail(AS_ERR_INVALID, "as_terminations_step: num_terms " + std::to_string(num_terms) +
+                                    " outside [1, AS_MAX_TERMINATION_TERMS = " +
+                                    std::to_string(AS_MAX_TERMINATION_TERMS) + "]");
+  if (n < 1 || n > AS_MAX_ENVS) return fail(AS_ERR_INVALID, "as_terminations_step: n outside [1, AS_MAX_ENVS]");
+  if (kinds >> AS_TERMINATION_NUM_KINDS)
+    return fail(AS_ERR_INVALID, "as_terminations_step: kinds has bits of unknown kinds");
+  const as_termination_sources_t& S = *sources;
+  if (S.joint_rows < 0 || S.command_terms < 0 || S.depth < 0 || S.bodies < 0)
+    return fail(AS_ERR_INVALID, "as_terminations_step: a negative row count");
+  auto missing = [&](int k, const char* what) {
+    return fail(AS_ERR_INVALID, std::string("as_terminations_step: a term of kind ") + std::to_string(k) +
+                                    " needs the source " + what + ", which is NULL or has no rows");
+  };
+  for (int k = 0; k < AS_TERMINATION_NUM_KINDS; ++k) {
+    if (!((kinds >> k) & 1u)) continue;
+    switch (k) {
+      case AS_TERMINATION_TIME_OUT:
+        if (!S.ep_len) return missing(k, "ep_len");
+        break;
+      case AS_TERMINATION_COMMAND_RESAMPLE:
+        if (!S.time_left || !S.command_counter || S.command_terms < 1)
+          return missing(k, "time_left / command_counter");
+        break;
+      case AS_TERMINATION_BAD_ORIENTATION:
+        if (!S.root_quat) return missing(k, "root_quat");
+        break;
+      case AS_TERMINATION_ROOT_HEIGHT_BELOW_MINIMUM:
+        if (!S.root_pos) return missing(k, "root_pos");
+        break;
+      case AS_TERMINATION_JOINT_POS_OUT_OF_LIMIT: case AS_TERMINATION_JOINT_POS_OUT_OF_MANUAL_LIMIT:
+        if (!S.q || S.joint_rows < 1) return missing(k, "q");
+        break;
+      case AS_TERMINATION_JOINT_VEL_OUT_OF_MANUAL_LIMIT:
+        if (!S.qd || S.joint_rows < 1) return missing(k, "qd");
+        break;
+      case AS_TERMINATION_ILLEGAL_CONTACT:
+        if (!S.net || S.depth < 1 || S.bodies < 1 || !std::isfinite(S.sim_dt) || !(S.sim_dt > 0.0f))
+          return missing(k, "net (and sim_dt)");
+        break;
+    }
+  }
+  as::TerminationsArgs a{};
+  a.terms = terms;
+  a.table = table;
+  a.num_terms = num_terms;
+  a.n = n;
+  a.src = S;
+  a.term_dones = term_dones;
+  a.time_outs = time_outs;
+  a.terminated = terminated;
+  a.dones = dones;
+  a.last_episode_dones = last_episode_dones;
+  a.reset_request = reset_request;
+  HIP_TRY(as::launch_terminations_step(a, reinterpret_cast<hipStream_t>(stream)));
+  return AS_OK;
+}
+
 int as_set_graph_safe(as_env_t* env, int32_t on) {
   if (!env) return fail(AS_ERR_INVALID, "as_set_graph_safe: null handle");
   env->graph_safe = on != 0;

@@ -264,6 +264,20 @@ struct RewardsArgs {
   float dt;
 };
 
+// k_terminations_step (as_terminations_step, termination_kernels.h): the terms of cfg.terminations
+struct TerminationsArgs {
+  const as_termination_term_t* terms;  // [num_terms] device memory
+  const float* table;  // [AS_TERMINATION_TABLE_ROWS][AS_MAX_TERMINATION_TERMS][AS_MAX_TERMINATION_IDS] words, device
+  int32_t num_terms, n;
+  as_termination_sources_t src;
+  uint8_t* term_dones;          // [num_terms][n]
+  uint8_t* time_outs;           // [n]
+  uint8_t* terminated;          // [n]
+  uint8_t* dones;               // [n]
+  uint8_t* last_episode_dones;  // [num_terms][n] or null: not written
+  uint8_t* reset_request;       // [n] or null: not written
+};
+
 // k_commands_step / k_commands_reset (as_commands_step / as_commands_reset, command_kernels.h): every buffer
 // field-major / env-minor.  k_commands_reset reads no root state, no dt and `reset` as its mask (null: every env)
 struct CommandsArgs {
@@ -358,6 +372,7 @@ hipError_t launch_observations(const ObservationsArgs& a, hipStream_t stream);
 hipError_t launch_observations_reset(const ObservationsArgs& a, hipStream_t stream);
 hipError_t launch_rewards_step(const RewardsArgs& a, hipStream_t stream);
 hipError_t launch_rewards_reset(const RewardsArgs& a, hipStream_t stream);
+hipError_t launch_terminations_step(const TerminationsArgs& a, hipStream_t stream);
 hipError_t launch_events_interval(const EventsArgs& a, hipStream_t stream);
 hipError_t launch_events_init(const EventsArgs& a, hipStream_t stream);
 hipError_t launch_noise_actions(const NoiseActArgs& a, hipStream_t stream);

@@ -28,8 +28,8 @@
 // contact_forces_kernel.h (k_contact_forces), noise_kernels.h, event_kernels.h, contact_timer_kernels.h
 // (k_contact_timers), ray_caster_kernels.h (k_ray_cast), imu_kernels.h (k_imu), ray_camera_kernels.h
 // (k_ray_camera), frame_transformer_kernels.h (k_frame_transformer), command_kernels.h (k_commands_step,
-// k_commands_reset), observation_kernels.h (k_observations, k_observations_reset) and reward_kernels.h
-// (k_rewards_step, k_rewards_reset).
+// k_commands_reset), observation_kernels.h (k_observations, k_observations_reset), reward_kernels.h
+// (k_rewards_step, k_rewards_reset) and termination_kernels.h (k_terminations_step).
 #include <hip/hip_runtime.h>
 
 #include "../../include/allsteps.h"
@@ -471,6 +471,7 @@ __global__ __launch_bounds__(kStepThreads) __attribute__((amdgpu_waves_per_eu(2,
 #include "command_kernels.h"
 #include "observation_kernels.h"
 #include "reward_kernels.h"
+#include "termination_kernels.h"
 
 namespace as {
 
@@ -575,6 +576,12 @@ hipError_t launch_rewards_step(const RewardsArgs& a, hipStream_t stream) {
 
 hipError_t launch_rewards_reset(const RewardsArgs& a, hipStream_t stream) {
   hipLaunchKernelGGL(k_rewards_reset, dim3((unsigned)((a.n + kRewThreads - 1) / kRewThreads)), dim3(kRewThreads), 0,
+                     stream, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_terminations_step(const TerminationsArgs& a, hipStream_t stream) {
+  hipLaunchKernelGGL(k_terminations_step, dim3((unsigned)((a.n + kTermEnvs - 1) / kTermEnvs)), dim3(kTermThreads), 0,
                      stream, a);
   return hipGetLastError();
 }

@@ -75,8 +75,19 @@ class AllstepsEnv(NativeDirectEnv):
         self.negation_body_indices = L(cfg.negation_body_names)
         self._observations_start()
         self._rewards_start()
+        self._terminations_start()
 
     _actions_clamped = True  # `actions` below
+
+    def _terminations_check_reset(self) -> None:
+        pass  # cfg.terminations_reset is served: as_reset_mask takes a device mask
+
+    def _terminations_reset_mask(self, mask: torch.Tensor, obs: torch.Tensor) -> None:
+        """cfg.terminations_reset: as_reset_mask on the manager's device mask.  As in _reset_idx, the curriculum
+        gate and the second foot-state tick run for every env when any env of the mask is reset, as the reference's
+        _reset_idx does; an all-zero mask leaves the state as it is.  The managers are not reset here: the step
+        hands the merged flags to them."""
+        self._native.reset_mask(mask, obs, None, stream=self._stream())
 
     # ------------------------------------------------------------------ task buffers (views)
     curr_target_index = property(lambda self: self.state["idx"])

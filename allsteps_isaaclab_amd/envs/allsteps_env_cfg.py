@@ -136,6 +136,15 @@ class AllstepsEnvCfg:
     # makes it the manager's.  Anything not served raises at construction.  None: nothing is allocated or launched.
     rewards: object = None
     rewards_replace_task_reward: bool = False
+    # Termination manager (the reference's ManagerBasedRLEnvCfg `terminations`): a dict or cfg object whose entries
+    # are utils.terminations TerminationTermCfg terms (None entries are skipped), or None.  The terms' flags,
+    # time_outs, terminated and dones are computed on the device by k_terminations_step
+    # (csrc/termination_kernels.h), one launch per step directly after the step, as env.termination_manager.
+    # step() returns the task's own dones and resets only what the task resets unless terminations_reset (the
+    # walker only), which also ends and resets the envs the manager's dones name.  Anything not served raises at
+    # construction.  None: nothing is allocated or launched.
+    terminations: object = None
+    terminations_reset: bool = False
 
     # joint gears, cfg/PhysX dof order (allsteps_env_cfg.py:133-155)
     joint_gears: list = field(default_factory=lambda: [

@@ -78,6 +78,13 @@ class AnymalCStonesEnv(NativeDirectEnv):
         self._actions = torch.zeros(n, self.num_dof, dtype=torch.float32, device=dev)
         self._observations_start()
         self._rewards_start()
+        self._terminations_start()
+
+    def _terminations_check_reset(self) -> None:
+        if getattr(self.cfg, "terminations_reset", False):
+            raise _native.NativeError("cfg.terminations_reset is not served by the quadruped: k_quad resets the envs "
+                                      "its own dones end and has no masked reset (DESIGN.md §9); leave it False -- "
+                                      "the termination manager then fills its own buffers")
 
     @property
     def actions(self) -> torch.Tensor:

@@ -46,6 +46,9 @@ class DirectRLEnv:
     # cfg.rewards (the reference's RewardManager): the device state of the reward kernel, built by _rewards_start
     # once the subclass has its views.  None: step() launches nothing for it.
     _rewards = None
+    # cfg.terminations (the reference's TerminationManager): the device state of the termination kernel, built by
+    # _terminations_start once the subclass has its views.  None: step() launches nothing for it.
+    _terminations = None
 
     def __init__(self, cfg, render_mode: str | None = None, **kwargs):
         self.cfg = cfg
@@ -159,13 +162,20 @@ class DirectRLEnv:
         their own buffers.  With cfg.rewards: the reward terms are computed in one launch after the sensors, the
         commands and the events and before the observation manager, on the state as the step left it (an env the
         step reset shows its post-reset state); the task's own reward is returned unless
-        cfg.rewards_replace_task_reward."""
+        cfg.rewards_replace_task_reward.  With cfg.terminations: the done terms are computed in one launch directly
+        after the step (after the once-per-step contact-force sums where a term reads them) and before everything
+        above -- the reference's order, terminations first -- on the state as the step left it; they fill the
+        manager's own buffers only, unless cfg.terminations_reset: then the envs the manager ends are reset by one
+        masked reset, their observation rows and flags join the step's, and every later stage of this step sees the
+        merged flags, so those envs are reset once, in the usual places."""
         action = action.to(self._device)
         self._sim_step_counter += self.cfg.decimation
         nz = self._noise
         if nz is not None and nz.action is not None:
             action = nz.apply_actions(action, self._noise_offset(), self._noise_stream())
         out = self._step_impl(action)
+        if self._terminations is not None:
+            out = self._terminations.apply(out)
         for sensor in self._lazy_sensors:  # (empty by default: the default step calls nothing)
             sensor.mark_dirty()
         if self._imus is not None:  # the step's sensor updates pass physics_dt (direct_rl_env.py:347)
@@ -351,6 +361,51 @@ class DirectRLEnv:
         if self._rewards is not None:
             self._rewards.set_state(state)
         return {k: v for k, v in state.items() if not EnvRewards.is_state_key(k)}
+
+    # ------------------------------------------------------------------ termination manager
+    def _terminations_start(self) -> None:
+        """Build the termination manager of cfg.terminations once the subclass has its state, views and sensors (its
+        constructor calls it beside _rewards_start); raises NativeError for a cfg the kernel does not serve."""
+        from .terminations import EnvTerminations, TerminationManagerView
+
+        self._terminations_check_reset()
+        if EnvTerminations.wanted(self.cfg):
+            self._terminations = EnvTerminations(self.cfg, self, self.num_envs, self._device)
+            self.termination_manager = TerminationManagerView(self._terminations)
+
+    def _terminations_check_reset(self) -> None:
+        """Raise NativeError where the env cannot serve cfg.terminations_reset (subclass hook)."""
+        if getattr(self.cfg, "terminations_reset", False):
+            from .. import _native
+
+            raise _native.NativeError(f"cfg.terminations_reset: {type(self).__name__} has no masked reset")
+
+    def _terminations_context(self):
+        """The TermContext of the env: what its terms can read (subclass hook)."""
+        raise NotImplementedError(f"{type(self).__name__} does not serve cfg.terminations")
+
+    def _terminations_sources(self, net: bool = False) -> dict:
+        """{source name: device tensor} of the rows the terms read; net: the contact report's dense net impulses
+        are wanted, brought up to date (subclass hook)."""
+        raise NotImplementedError(f"{type(self).__name__} does not serve cfg.terminations")
+
+    def _terminations_reset_mask(self, mask: torch.Tensor, obs: torch.Tensor) -> None:
+        """Reset the envs of a device uint8 mask and write every env's observation row into ``obs``: one
+        stream-ordered masked reset, no host read (subclass hook of cfg.terminations_reset)."""
+        raise NotImplementedError(f"{type(self).__name__} does not serve cfg.terminations_reset")
+
+    def _terminations_get_state(self) -> dict:
+        """The term flags, time_outs / terminated / dones, the last episode's flags and the reset request (no keys
+        without cfg.terminations)."""
+        return {} if self._terminations is None else self._terminations.get_state()
+
+    def _terminations_set_state(self, state: dict) -> dict:
+        """Load the termination keys of a set_state dict; returns the dict without them."""
+        from .terminations import EnvTerminations
+
+        if self._terminations is not None:
+            self._terminations.set_state(state)
+        return {k: v for k, v in state.items() if not EnvTerminations.is_state_key(k)}
 
     @staticmethod
     def seed(seed: int = -1) -> int:

@@ -9,8 +9,8 @@ import torch
 from .. import _native
 from .direct_rl_env import DirectRLEnv
 from .state import alloc_state
-from .views import (_ContactReport, _ContactTimers, _FootSensor, _FrameTransformerSet, _ImuSet, _RayCaster,
-                    _RayCasterCamera)
+from .views import (_ContactReport, _ContactSensor, _ContactTimers, _FootSensor, _FrameTransformerSet, _ImuSet,
+                    _RayCaster, _RayCasterCamera)
 
 
 class NativeDirectEnv(DirectRLEnv):
@@ -28,7 +28,8 @@ class NativeDirectEnv(DirectRLEnv):
         ``env.scene.sensors["height_scanner"]``), with ``cfg.camera`` the ray-cast cameras (``env.scene.sensors[name]``;
         ``env.camera`` for a single cfg), with ``cfg.imu`` the IMUs (``env.scene.sensors[name]``; ``env.imu``
         for a single cfg), with ``cfg.frame_transformer`` the frame transformers (``env.scene.sensors[name]``;
-        ``env.frame_transformer`` for a single cfg).  Env-specific initial values are the caller's."""
+        ``env.frame_transformer`` for a single cfg); with ``cfg.contact_forces`` the all-body contact sensor
+        (``env.scene.sensors["contact_forces"]``).  Env-specific initial values are the caller's."""
         dev = self._device
         if dev.type != "cuda" or not torch.cuda.is_available():
             raise _native.NativeError(f"{type(self).__name__} runs on the HIP backend only (device={dev}, HIP device "
@@ -47,6 +48,8 @@ class NativeDirectEnv(DirectRLEnv):
             self._contact_timers = (_ContactTimers(self, self._report, self.cfg.contact_force_threshold)
                                     if air else None)
             self._sensors = self._contact_timers  # DirectRLEnv.step / reset drive them
+            if on:  # the net forces of every body of the robot, over the report's one launch per step
+                self.scene.sensors["contact_forces"] = _ContactSensor(self, self._report)
             hs = getattr(self.cfg, "height_scanner", None)
             if hs is not None:  # lazy: launched by reads of its data (or update(force_recompute=True)), never by step
                 self.height_scanner = self.scene.sensors["height_scanner"] = _RayCaster(self, hs)
@@ -159,6 +162,34 @@ class NativeDirectEnv(DirectRLEnv):
                 "net": rep.forces()[1] if (net and rep is not None) else None,
                 "timers": None if tm is None else tm.timers}
 
+    def _terminations_context(self):
+        from .terminations import SensorInfo, TermContext
+
+        d = self.robot.data
+        rep = self._report
+        sensors = {}
+        for name, s in vars(self).items():  # the env's foot sensors, under their attribute names
+            if isinstance(s, _FootSensor):
+                sensors[name] = SensorInfo(list(s.body_names), [0 if rep is None else rep.foot_body[f] for f in s._feet])
+        for name, s in self.scene.sensors.items():  # and the all-body contact sensor of cfg.contact_forces
+            if isinstance(s, _ContactSensor):
+                sensors[name] = SensorInfo(list(s.body_names), list(range(s.num_bodies)))
+        return TermContext(
+            joint_names=list(d.joint_names),
+            soft_joint_pos_limits=d.soft_joint_pos_limits[0].detach().cpu().numpy(),
+            step_dt=self.step_dt, max_episode_length=self.max_episode_length,
+            command_names=[] if self._commands is None else list(self._commands.terms.names),
+            sensors=sensors, contact_forces=rep is not None)
+
+    def _terminations_sources(self, net: bool = False) -> dict:
+        s, cm, rep = self.state, self._commands, self._report
+        nd = int(self.model["num_hinges"])
+        has_cm = cm is not None and len(cm.terms.names)
+        return {"root_pos": s["root_pos"], "root_quat": s["root_quat"], "q": s["q"][:nd], "qd": s["qd"][:nd],
+                "ep_len": s["ep_len"],
+                "time_left": cm.time_left if has_cm else None, "command_counter": cm.counter if has_cm else None,
+                "net": rep.forces()[1] if (net and rep is not None) else None}
+
     def _report_or_raise(self, what: str) -> _ContactReport:
         if self._report is None:
             raise _native.NativeError(
@@ -191,11 +222,14 @@ class NativeDirectEnv(DirectRLEnv):
         streams' counters, the push counts and each group's output rows, which hold its history (observation_t,
         observation_count, (groups, N) each; observation_history_<group>, (N, columns)); with cfg.rewards, the
         reward manager's episodic sums, step values and last episode's sums ((terms, N) each) and its previous
-        actions (reward_episode_sums, reward_step, reward_last_episode_sums, reward_prev_actions)."""
+        actions (reward_episode_sums, reward_step, reward_last_episode_sums, reward_prev_actions); with
+        cfg.terminations, the termination manager's flags (termination_term_dones, termination_last_episode_dones,
+        (terms, N); termination_time_outs, termination_terminated, termination_dones, termination_reset_request,
+        (N,); uint8)."""
         tm, im = self._contact_timers, self._imus
         return {**{k: v.clone() for k, v in self.state.items()}, **self._noise_get_state(),
                 **self._events_get_state(), **self._commands_get_state(), **self._observations_get_state(),
-                **self._rewards_get_state(),
+                **self._rewards_get_state(), **self._terminations_get_state(),
                 **({} if tm is None else tm.get_state()),
                 **({} if im is None else im.get_state())}
 
@@ -206,7 +240,7 @@ class NativeDirectEnv(DirectRLEnv):
         if self._imus is not None:  # (and every env is outdated)
             self._imus.set_state(state)
         state = {k: v for k, v in state.items() if k not in _ContactTimers.STATE_KEYS + _ImuSet.STATE_KEYS}
-        state = self._rewards_set_state(self._observations_set_state(state))
+        state = self._terminations_set_state(self._rewards_set_state(self._observations_set_state(state)))
         for k, v in self._commands_set_state(self._events_set_state(self._noise_set_state(state))).items():
             self.state[k].copy_(torch.as_tensor(v).to(self.state[k].device, self.state[k].dtype).reshape(
                 self.state[k].shape))

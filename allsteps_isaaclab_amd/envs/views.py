@@ -304,6 +304,50 @@ class _ContactReport:
         return self._matrix, self._net
 
 
+class _ContactSensorData:
+    def __init__(self, sensor: "_ContactSensor"):
+        self._sensor = sensor
+
+    @property
+    def net_forces_w_history(self) -> torch.Tensor:
+        """(N, T, B, 3) net normal contact force on every body of the robot over the env step's last T = decimation
+        substeps, index 0 the latest: the contact report's net impulses / sim.dt, as the foot sensors form theirs."""
+        return self._sensor._report.forces()[1].permute(3, 0, 1, 2) / self._sensor._env.cfg.sim.dt
+
+    @property
+    def net_forces_w(self) -> torch.Tensor:
+        """(N, B, 3) the net forces of the last substep."""
+        return self.net_forces_w_history[:, 0]
+
+
+class _ContactSensor:
+    """``env.scene.sensors["contact_forces"]`` of an env with ``cfg.contact_forces``: a contact sensor over every
+    body of the robot (``body_names``: the articulation's, in its order), the view the velocity task's
+    ``illegal_contact`` on the base reads.  It is built over the contact report's dense net impulses
+    (``_ContactReport.forces()[1]``, one launch per step however many views read it) and launches nothing itself."""
+
+    def __init__(self, env, report: "_ContactReport"):
+        self._env, self._report = env, report
+        self.body_names = list(env.model["body_names"])[: int(env.model["num_bodies"])]
+        self.num_bodies = len(self.body_names)
+        self.data = _ContactSensorData(self)
+
+    def find_bodies(self, name_keys, preserve_order: bool = False):
+        """(indices, names) of the bodies whose whole name matches one of the regular expressions ``name_keys`` (a
+        string or a list), in body order, or in the order of the keys with ``preserve_order``
+        (contact_sensor.py ``find_bodies``); a key that matches nothing is a ValueError."""
+        import re
+
+        keys = [name_keys] if isinstance(name_keys, str) else list(name_keys)
+        hit = [[k for k, bn in enumerate(self.body_names) if re.fullmatch(p, bn)] for p in keys]
+        missing = [p for p, h in zip(keys, hit) if not h]
+        if missing:
+            raise ValueError(f"find_bodies: {missing} match no body of {self.body_names}")
+        flat = [k for h in hit for k in h]
+        ids = list(dict.fromkeys(flat)) if preserve_order else sorted(set(flat))
+        return ids, [self.body_names[k] for k in ids]
+
+
 class _ContactTimers:
     """The air / contact timers of an env (``cfg.contact_air_time``; the reference's ContactSensor with
     track_air_time = True, contact_sensor.py:351-379): device state of ``as_contact_timers`` over the env's contact
@@ -866,4 +910,8 @@ def __getattr__(name: str):
         from .rewards import RewardManagerView
 
         return RewardManagerView
+    if name == "TerminationManagerView":  # (``env.termination_manager``, envs/terminations.py: the same)
+        from .terminations import TerminationManagerView
+
+        return TerminationManagerView
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

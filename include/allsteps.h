@@ -754,6 +754,66 @@ int as_rewards_step(const as_reward_term_t* terms, int32_t num_terms, const floa
 int as_rewards_reset(float* episode_sums, int32_t num_terms, float* prev_actions, int32_t action_cols,
                      const uint8_t* mask, int32_t n, void* stream);
 
+/* Termination manager, off by default: the done terms of cfg.terminations (isaaclab/managers/termination_manager.py,
+ * the term functions of isaaclab/envs/mdp/terminations.py).  One launch computes every term of every env: per term in
+ * cfg order term_dones[k] = f, and time_outs |= f for a term with time_out != 0, terminated |= f otherwise, both
+ * started at 0; dones = time_outs | terminated.  Then, for an env with dones | step_terminated | step_truncated:
+ * last_episode_dones[k] = term_dones[k] for every term (what the reference's reset would count, as a captured step
+ * serves it); and reset_request = dones & ~(step_terminated | step_truncated): the envs the manager ends and the step
+ * did not reset itself.  The caller launches it directly after as_step (and as_contact_forces where a term reads the
+ * net forces) on the same stream; the state rows of an env the step reset are the post-reset ones.  A stateless
+ * entry point over caller-owned device buffers -- no as_env_t.  Every buffer is field-major / env-minor ([rows][n]).
+ * Formulas and the float32 operations: csrc/allsteps_terminations.h.  Graph-safe: the term descriptors and the index
+ * table are read from device memory at every launch.  Symbols added only: AS_ABI_VERSION stays 6. */
+#define AS_MAX_TERMINATION_TERMS 16
+#define AS_MAX_TERMINATION_IDS 32   /* entries of a term's row of the index table (joints or bodies) */
+#define AS_TERMINATION_TABLE_ROWS 3 /* table [3][AS_MAX_TERMINATION_TERMS][AS_MAX_TERMINATION_IDS] words: id | a | b */
+enum {
+  AS_TERMINATION_TIME_OUT = 0,            /* step_truncated | (ep_len >= i0)             i0 max_episode_length */
+  AS_TERMINATION_COMMAND_RESAMPLE,        /* (time_left[row] <= p0) & (command_counter[row] == i0)   p0 step_dt */
+  AS_TERMINATION_BAD_ORIENTATION,         /* |acos(-projected_gravity_b[2])| > p0        p0 limit_angle */
+  AS_TERMINATION_ROOT_HEIGHT_BELOW_MINIMUM, /* root_pos[2] < p0                          p0 minimum_height */
+  AS_TERMINATION_JOINT_POS_OUT_OF_LIMIT,  /* any q[id] > b or q[id] < a                  a, b the soft limits */
+  AS_TERMINATION_JOINT_POS_OUT_OF_MANUAL_LIMIT, /* any q[id] > p1 or q[id] < p0          p0, p1 the bounds */
+  AS_TERMINATION_JOINT_VEL_OUT_OF_MANUAL_LIMIT, /* any |qd[id]| > p0                     p0 max_velocity */
+  AS_TERMINATION_ILLEGAL_CONTACT,         /* any body whose max-over-slots |net / sim_dt| > p0   p0 threshold */
+  AS_TERMINATION_NUM_KINDS
+};
+typedef struct {
+  int32_t kind;      /* AS_TERMINATION_* */
+  int32_t time_out;  /* != 0: the term is a time-out, it enters time_outs; 0: terminated */
+  int32_t num_ids;   /* entries of the term's index-table row, <= AS_MAX_TERMINATION_IDS */
+  int32_t row;       /* the command term's row of time_left / command_counter */
+  float p0, p1;      /* the kind's constants, formed by the host as float32 the way torch takes a Python scalar */
+  int32_t i0;        /* max_episode_length / num_resamples */
+  int32_t reserved0;
+} as_termination_term_t;
+typedef struct {
+  const float* root_pos;            /* [3][n] */
+  const float* root_quat;           /* [4][n] (w x y z) */
+  const float* q;                   /* [joint_rows][n] */
+  const float* qd;                  /* [joint_rows][n] */
+  const float* time_left;           /* [command_terms][n] the command manager's, or NULL */
+  const int32_t* command_counter;   /* [command_terms][n] the command manager's, or NULL */
+  const float* net;                 /* [depth][bodies][3][n] as_contact_forces' net impulses, or NULL */
+  const int32_t* ep_len;            /* [n] the step's episode length counter, or NULL */
+  const uint8_t* step_terminated;   /* [n] the step's own flags: the step reset these envs itself; NULL: 0 */
+  const uint8_t* step_truncated;    /* [n] or NULL: 0 */
+  int32_t joint_rows, command_terms, depth, bodies;
+  float sim_dt;                     /* the physics step: impulses / sim_dt are forces */
+} as_termination_sources_t;
+/* terms [num_terms] and table [AS_TERMINATION_TABLE_ROWS][AS_MAX_TERMINATION_TERMS][AS_MAX_TERMINATION_IDS] are
+ * device memory.  kinds: bit k set for every AS_TERMINATION_* kind a descriptor may hold (the host's knowledge of the
+ * device descriptors): a set bit whose source pointer is NULL is AS_ERR_INVALID, as are NULL terms / table / sources
+ * / term_dones / time_outs / terminated / dones and num_terms outside [1, AS_MAX_TERMINATION_TERMS] -- all before
+ * any device call.  A source that is NULL, or an id outside its rows, reads as 0 on the device.  term_dones and
+ * last_episode_dones [num_terms][n], time_outs, terminated, dones and reset_request [n], all uint8 0 / 1;
+ * last_episode_dones and reset_request may be NULL (not written). */
+int as_terminations_step(const as_termination_term_t* terms, int32_t num_terms, const float* table, uint32_t kinds,
+                         const as_termination_sources_t* sources, uint8_t* term_dones, uint8_t* time_outs,
+                         uint8_t* terminated, uint8_t* dones, uint8_t* last_episode_dones, uint8_t* reset_request,
+                         int32_t n, void* stream);
+
 /* The H^-1 sweep plan for a model (round 6, ABI 5; no device needed). The step kernel sweeps the
  * padded joint-space inertia last block first and, for the trees it is compiled for (the walker, the
  * C5 quadruped), skips the column quads in which the pivot rows are structurally zero -- an exact
