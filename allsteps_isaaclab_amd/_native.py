@@ -30,6 +30,7 @@ EXPORTED_SYMBOLS = [
     "as_contact_timers", "as_ray_cast", "as_imu", "as_ray_camera",
     "as_frame_transformer", "as_commands_step", "as_commands_reset", "as_observations_step",
     "as_observations_reset", "as_rewards_step", "as_rewards_reset", "as_terminations_step",
+    "as_actions_step", "as_actions_reset", "as_set_joint_commands",
 ]
 MAXB = 32  # AS_MAX_BODIES
 MAXC = 10  # AS_MAX_CONTACTS
@@ -362,6 +363,30 @@ def terminations_step(terms, table, kinds: int, sources: AsTerminationSources, t
                                       dones.shape[0], stream), "as_terminations_step")
 
 
+ACT_DIM = 21  # AS_ACT_DIM: the most columns of cfg.actions, the most joints of a command row
+ACTION_KINDS = ("joint_position", "joint_effort", "position_to_limits", "ema_position_to_limits")  # AS_ACTION_*
+# as_action_column_t as 12 32-bit words: joint, kind, rescale, term (int32) | scale, offset, clip_lo, clip_hi, lim_lo,
+# lim_hi, alpha, one_minus_alpha (float32)
+ACTION_COLUMN_WORDS = 12
+
+
+def actions_step(cols, inp, action, prev_action, processed, prev_applied, cmd, stream=None):
+    """as_actions_step: process_action of every column of cfg.actions in one launch.  cols (num_cols, 12) float32
+    device rows of as_action_column_t; inp / action / prev_action / processed / prev_applied (n, num_cols) and cmd
+    (n, joints), float32, contiguous."""
+    check(load().as_actions_step(cols.data_ptr(), cols.shape[0], inp.data_ptr(), action.data_ptr(),
+                                 prev_action.data_ptr(), processed.data_ptr(), prev_applied.data_ptr(),
+                                 cmd.data_ptr(), cmd.shape[1], action.shape[0], stream), "as_actions_step")
+
+
+def actions_reset(cols, action, prev_action, prev_applied, q, mask=None, mask2=None, stream=None):
+    """as_actions_reset: ActionManager.reset over the envs of mask | mask2 ((n,) uint8 / bool; neither: every env);
+    q (joints, n) float32 the joint positions, cfg dof order."""
+    check(load().as_actions_reset(cols.data_ptr(), cols.shape[0], action.data_ptr(), prev_action.data_ptr(),
+                                  prev_applied.data_ptr(), q.data_ptr(), q.shape[0], _ptr(mask), _ptr(mask2),
+                                  action.shape[0], stream), "as_actions_reset")
+
+
 def unpack_report_ids(w):
     """(link, link2, stone, foot) of a record's ids word (int array or tensor); -1 = none."""
     return w & 0xFF, (w >> 8 & 0xFF) - 1, (w >> 16 & 0xFF) - 1, (w >> 24 & 0xFF) - 1
@@ -545,6 +570,9 @@ def load() -> C.CDLL:
     L.as_rewards_step.argtypes = [V, I32, V, C.c_uint32, V, V, V, V, V, V, V, V, I32, C.c_float, V]
     L.as_rewards_reset.argtypes = [V, I32, V, I32, V, I32, V]
     L.as_terminations_step.argtypes = [V, I32, V, C.c_uint32, V, V, V, V, V, V, V, I32, V]
+    L.as_actions_step.argtypes = [V, I32, V, V, V, V, V, V, I32, I32, V]
+    L.as_actions_reset.argtypes = [V, I32, V, V, V, V, I32, V, V, I32, V]
+    L.as_set_joint_commands.argtypes = [V, V]
     L.as_last_error.restype = C.c_char_p
     L.as_build_id.restype = C.c_char_p
     for name in EXPORTED_SYMBOLS:
@@ -758,6 +786,16 @@ class NativeEnv:
         R.count, R.records, R.qd_prev = (_ptr(t) for t in (count, records, qd_prev))
         check(self.L.as_set_contact_report(self.h, C.byref(R)), "as_set_contact_report")
         self._report = (R, count, records, qd_prev)
+
+    def set_joint_commands(self, cmd=None):
+        """as_set_joint_commands: every later physics launch reads its joint commands from cmd, float32 (n, joints)
+        on the device (kept alive here), in place of the actuator's own formula; None: off."""
+        if cmd is not None and (tuple(cmd.shape) != (self.n, int(self._model.num_hinges)) or
+                                not cmd.is_contiguous() or str(cmd.dtype) != "torch.float32" or not cmd.is_cuda):
+            raise NativeError(f"as_set_joint_commands: cmd must be a contiguous float32 device tensor of shape "
+                              f"({self.n}, {int(self._model.num_hinges)})")
+        check(self.L.as_set_joint_commands(self.h, _ptr(cmd)), "as_set_joint_commands")
+        self._joint_cmd = cmd
 
     def contact_forces(self, table: "AsBodyTable", force_matrix_out, net_out, stream=None):
         """as_contact_forces: force_matrix_out fp32 [depth][REPORT_FEET][NUM_STONES][3][n], net_out fp32

@@ -2,9 +2,15 @@
 observation over the device ray caster, the image observation over the device ray-cast camera, the IMU
 observations over the device IMU kernel, the velocity command cfgs and ``generated_commands`` over the device
 command kernel, the observation functions the device observation kernel serves, the reward functions the device
-reward kernel serves (those of the velocity task's ``mdp`` among them), and the termination functions the device
-termination kernel serves."""
+reward kernel serves (those of the velocity task's ``mdp`` among them), the termination functions the device
+termination kernel serves, and the action term cfgs of ``isaaclab.envs.mdp.actions``: the joint terms the device
+action kernels serve, and the others, which import and are refused by the envs with their reason."""
 
+from allsteps_isaaclab_amd.utils.actions import (  # noqa: F401
+    JointActionCfg, JointPositionActionCfg, JointEffortActionCfg, JointPositionToLimitsActionCfg,
+    EMAJointPositionToLimitsActionCfg, RelativeJointPositionActionCfg, JointVelocityActionCfg, BinaryJointActionCfg,
+    BinaryJointPositionActionCfg, BinaryJointVelocityActionCfg, NonHolonomicActionCfg,
+    DifferentialInverseKinematicsActionCfg, OperationalSpaceControllerActionCfg)
 from allsteps_isaaclab_amd.utils.commands import (  # noqa: F401
     NormalVelocityCommandCfg, NullCommandCfg, UniformVelocityCommandCfg, generated_commands)
 from allsteps_isaaclab_amd.utils.events import push_by_setting_velocity  # noqa: F401
@@ -38,4 +44,8 @@ __all__ = ["push_by_setting_velocity", "height_scan", "image", "imu_orientation"
            "feet_slide", "track_lin_vel_xy_yaw_frame_exp", "track_ang_vel_z_world_exp",
            "time_out", "command_resample", "bad_orientation", "root_height_below_minimum", "joint_pos_out_of_limit",
            "joint_pos_out_of_manual_limit", "joint_vel_out_of_limit", "joint_vel_out_of_manual_limit",
-           "joint_effort_out_of_limit", "illegal_contact"]
+           "joint_effort_out_of_limit", "illegal_contact",
+           "JointActionCfg", "JointPositionActionCfg", "JointEffortActionCfg", "JointPositionToLimitsActionCfg",
+           "EMAJointPositionToLimitsActionCfg", "RelativeJointPositionActionCfg", "JointVelocityActionCfg",
+           "BinaryJointActionCfg", "BinaryJointPositionActionCfg", "BinaryJointVelocityActionCfg",
+           "NonHolonomicActionCfg", "DifferentialInverseKinematicsActionCfg", "OperationalSpaceControllerActionCfg"]

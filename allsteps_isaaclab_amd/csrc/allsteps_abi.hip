@@ -73,6 +73,7 @@ struct as_env {
   unsigned long long* stamps = nullptr;  // diagnostic (as_debug_stamps)
   as_contact_report_t report{};          // as_set_contact_report (count == nullptr: off)
   as::ReportDesc* report_dev = nullptr;  // its device copy, the block the launches point at
+  const float* joint_cmd = nullptr;      // as_set_joint_commands (nullptr: off)
   int32_t prof_cap = 0, prof_n = 0, prof_stride = 1, prof_calls = 0;
 };
 
@@ -259,6 +260,8 @@ static int run(as_env_t* env, int mode, const float* actions, float* obs, float*
   a.side = env->side_dev;
   a.wave_map = env->wave_map_dev;
   a.rep = env->report.count ? env->report_dev : nullptr;
+  // the joint commands serve the physics only: reset and task-only launches ignore them
+  a.cmd = (mode == as::kModeStep || mode == as::kModePhysics) ? env->joint_cmd : nullptr;
   const bool prof = env->prof_n < env->prof_cap && (env->prof_calls++ % env->prof_stride) == 0;
   if (prof) HIP_TRY(hipEventRecord(env->ev[3 * env->prof_n], s));
   HIP_TRY(as::launch_step(a, env->nv, env->sweep_skip, s));
@@ -504,6 +507,12 @@ int as_set_contact_report(as_env_t* env, const as_contact_report_t* report) {
   HIP_TRY(hipDeviceSynchronize());
   HIP_TRY(hipMemcpy(env->report_dev, &d, sizeof(d), hipMemcpyHostToDevice));
   env->report = *report;
+  return AS_OK;
+}
+
+int as_set_joint_commands(as_env_t* env, const float* cmd_dev) {
+  if (!env) return fail(AS_ERR_INVALID, "as_set_joint_commands: null handle");
+  env->joint_cmd = cmd_dev;  // a launch argument: it holds from the next launch on
   return AS_OK;
 }
 
@@ -1187,6 +1196,64 @@ int as_terminations_step(const as_termination_term_t* terms, int32_t num_terms, 
   a.last_episode_dones = last_episode_dones;
   a.reset_request = reset_request;
   HIP_TRY(as::launch_terminations_step(a, reinterpret_cast<hipStream_t>(stream)));
+  return AS_OK;
+}
+
+static int actions_check(const char* who, const as_action_column_t* cols, int32_t num_cols, int32_t cmd_cols,
+                         int32_t n) {
+  if (!cols) return fail(AS_ERR_INVALID, std::string(who) + ": null cols");
+  if (num_cols < 1 || num_cols > AS_ACT_DIM)
+    return fail(AS_ERR_INVALID, std::string(who) + ": num_cols " + std::to_string(num_cols) +
+                                    " outside [1, AS_ACT_DIM = " + std::to_string(AS_ACT_DIM) + "]");
+  if (cmd_cols < 1 || cmd_cols > AS_ACT_DIM)
+    return fail(AS_ERR_INVALID, std::string(who) + ": joint count " + std::to_string(cmd_cols) +
+                                    " outside [1, AS_ACT_DIM = " + std::to_string(AS_ACT_DIM) + "]");
+  if (n < 1 || n > AS_MAX_ENVS) return fail(AS_ERR_INVALID, std::string(who) + ": n outside [1, AS_MAX_ENVS]");
+  return AS_OK;
+}
+
+int as_actions_step(const as_action_column_t* cols, int32_t num_cols, const float* input, float* action,
+                    float* prev_action, float* processed, float* prev_applied, float* cmd, int32_t cmd_cols,
+                    int32_t n, void* stream) {
+  const int rc = actions_check("as_actions_step", cols, num_cols, cmd_cols, n);
+  if (rc != AS_OK) return rc;
+  if (!input || !action || !prev_action || !processed || !prev_applied || !cmd)
+    return fail(AS_ERR_INVALID, "as_actions_step: null argument (input / action / prev_action / processed / "
+                                "prev_applied / cmd)");
+  as::ActionsArgs a{};
+  a.cols = cols;
+  a.num_cols = num_cols;
+  a.cmd_cols = cmd_cols;
+  a.n = n;
+  a.input = input;
+  a.action = action;
+  a.prev_action = prev_action;
+  a.processed = processed;
+  a.prev_applied = prev_applied;
+  a.cmd = cmd;
+  HIP_TRY(as::launch_actions_process(a, reinterpret_cast<hipStream_t>(stream)));
+  return AS_OK;
+}
+
+int as_actions_reset(const as_action_column_t* cols, int32_t num_cols, float* action, float* prev_action,
+                     float* prev_applied, const float* q, int32_t q_rows, const uint8_t* mask, const uint8_t* mask2,
+                     int32_t n, void* stream) {
+  const int rc = actions_check("as_actions_reset", cols, num_cols, q_rows, n);
+  if (rc != AS_OK) return rc;
+  if (!action || !prev_action || !prev_applied || !q)
+    return fail(AS_ERR_INVALID, "as_actions_reset: null argument (action / prev_action / prev_applied / q)");
+  as::ActionsArgs a{};
+  a.cols = cols;
+  a.num_cols = num_cols;
+  a.cmd_cols = q_rows;
+  a.n = n;
+  a.action = action;
+  a.prev_action = prev_action;
+  a.prev_applied = prev_applied;
+  a.q = q;
+  a.mask = mask;
+  a.mask2 = mask2;
+  HIP_TRY(as::launch_actions_reset(a, reinterpret_cast<hipStream_t>(stream)));
   return AS_OK;
 }
 

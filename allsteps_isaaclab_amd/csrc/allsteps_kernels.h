@@ -43,6 +43,8 @@ struct StepArgs {
   unsigned long long* stamps;  // diagnostic phase timing (s_memtime deltas summed over waves) or null
   const int32_t* wave_map;     // [2 * blocks] env of each workgroup half (see kMapEnvs) or null: xcd_block
   const ReportDesc* rep;       // the opt-in contact report (step_report.h), or null: off
+  const float* cmd;            // the opt-in joint commands [n][num_hinges] (as_set_joint_commands) of a physics
+                               // launch, or null: the hard-wired action formulas
 };
 
 // phase ids of the diagnostic stamps (as_debug_stamps)
@@ -278,6 +280,22 @@ struct TerminationsArgs {
   uint8_t* reset_request;       // [n] or null: not written
 };
 
+// k_actions_process / k_actions_reset (as_actions_step / as_actions_reset, action_kernels.h): the joint terms of
+// cfg.actions.  The per-column buffers are env-major [n][num_cols]
+struct ActionsArgs {
+  const as_action_column_t* cols;  // [num_cols] device memory
+  int32_t num_cols, cmd_cols, n;   // cmd_cols: the robot's hinges, the rows of q and the columns of cmd
+  const float* input;              // [n][num_cols] the policy's action (process only)
+  float* action;                   // [n][num_cols]
+  float* prev_action;              // [n][num_cols]
+  float* processed;                // [n][num_cols] (process only)
+  float* prev_applied;             // [n][num_cols] the EMA columns' state
+  float* cmd;                      // [n][cmd_cols] the joint commands, cfg dof order (process only)
+  const float* q;                  // [cmd_cols][n] joint positions (reset only)
+  const uint8_t* mask;             // [n] reset: the envs to reset, with mask2; both null: every env
+  const uint8_t* mask2;
+};
+
 // k_commands_step / k_commands_reset (as_commands_step / as_commands_reset, command_kernels.h): every buffer
 // field-major / env-minor.  k_commands_reset reads no root state, no dt and `reset` as its mask (null: every env)
 struct CommandsArgs {
@@ -373,6 +391,8 @@ hipError_t launch_observations_reset(const ObservationsArgs& a, hipStream_t stre
 hipError_t launch_rewards_step(const RewardsArgs& a, hipStream_t stream);
 hipError_t launch_rewards_reset(const RewardsArgs& a, hipStream_t stream);
 hipError_t launch_terminations_step(const TerminationsArgs& a, hipStream_t stream);
+hipError_t launch_actions_process(const ActionsArgs& a, hipStream_t stream);
+hipError_t launch_actions_reset(const ActionsArgs& a, hipStream_t stream);
 hipError_t launch_events_interval(const EventsArgs& a, hipStream_t stream);
 hipError_t launch_events_init(const EventsArgs& a, hipStream_t stream);
 hipError_t launch_noise_actions(const NoiseActArgs& a, hipStream_t stream);

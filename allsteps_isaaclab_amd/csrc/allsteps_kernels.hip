@@ -29,7 +29,8 @@
 // (k_contact_timers), ray_caster_kernels.h (k_ray_cast), imu_kernels.h (k_imu), ray_camera_kernels.h
 // (k_ray_camera), frame_transformer_kernels.h (k_frame_transformer), command_kernels.h (k_commands_step,
 // k_commands_reset), observation_kernels.h (k_observations, k_observations_reset), reward_kernels.h
-// (k_rewards_step, k_rewards_reset) and termination_kernels.h (k_terminations_step).
+// (k_rewards_step, k_rewards_reset), termination_kernels.h (k_terminations_step) and action_kernels.h
+// (k_actions_process, k_actions_reset).
 #include <hip/hip_runtime.h>
 
 #include "../../include/allsteps.h"
@@ -96,6 +97,11 @@ __global__ __launch_bounds__(kStepThreads) __attribute__((amdgpu_waves_per_eu(2,
   const float* actp = P.mode != kModeReset ? P.actions : st.q;
   float v_a = actp[(size_t)e * nh + lh];
   if (P.mode == kModeReset) v_a = 0.f;
+  // the opt-in joint commands (as_set_joint_commands; the host passes them to physics launches only): lane lh's
+  // command, loaded unconditionally in this batch at a pointer that falls back to the actions', so no branch and
+  // no wait of its own is added
+  const float* cmdp = P.cmd ? P.cmd : actp;
+  const float v_c = cmdp[(size_t)e * nh + lh];
   const float v_s0 = st.stones[k0 * n + e], v_s1 = st.stones[k1 * n + e];
   uint32_t mask[4] = {st.contact_mask[e], st.contact_mask[n + e], 0u, 0u};
   uint32_t v_pk;
@@ -153,6 +159,10 @@ __global__ __launch_bounds__(kStepThreads) __attribute__((amdgpu_waves_per_eu(2,
     s.act[lane] = a;
     s.tau[i] = gain * row_gear * a;                      // allsteps_env.py:273
     s.qt[i] = Kc->act.action_scale * a + row_dq;         // AS_ACT_DC_MOTOR (anymal_c_env.py:73-74)
+    if (P.cmd) {  // an action manager's command is the applied effort / the target itself: no gain, gear or clip
+      s.tau[i] = v_c;
+      s.qt[i] = v_c;
+    }
   }
   if (lane < ns3) s.stones[lane] = v_s0;
   if (lane + G < ns3) s.stones[lane + G] = v_s1;
@@ -472,6 +482,7 @@ __global__ __launch_bounds__(kStepThreads) __attribute__((amdgpu_waves_per_eu(2,
 #include "observation_kernels.h"
 #include "reward_kernels.h"
 #include "termination_kernels.h"
+#include "action_kernels.h"
 
 namespace as {
 
@@ -583,6 +594,20 @@ hipError_t launch_rewards_reset(const RewardsArgs& a, hipStream_t stream) {
 hipError_t launch_terminations_step(const TerminationsArgs& a, hipStream_t stream) {
   hipLaunchKernelGGL(k_terminations_step, dim3((unsigned)((a.n + kTermEnvs - 1) / kTermEnvs)), dim3(kTermThreads), 0,
                      stream, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_actions_process(const ActionsArgs& a, hipStream_t stream) {
+  const int64_t total = (int64_t)a.n * a.num_cols;
+  hipLaunchKernelGGL(k_actions_process, dim3((unsigned)((total + kActionThreads - 1) / kActionThreads)),
+                     dim3(kActionThreads), 0, stream, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_actions_reset(const ActionsArgs& a, hipStream_t stream) {
+  const int64_t total = (int64_t)a.n * a.num_cols;
+  hipLaunchKernelGGL(k_actions_reset, dim3((unsigned)((total + kActionThreads - 1) / kActionThreads)),
+                     dim3(kActionThreads), 0, stream, a);
   return hipGetLastError();
 }
 

@@ -73,6 +73,7 @@ class AllstepsEnv(NativeDirectEnv):
         self.right_body_indices = L(cfg.right_body_names)
         self.left_body_indices = L(cfg.left_body_names)
         self.negation_body_indices = L(cfg.negation_body_names)
+        self._actions_start()
         self._observations_start()
         self._rewards_start()
         self._terminations_start()
@@ -194,7 +195,12 @@ class AllstepsEnv(NativeDirectEnv):
     def step_with_draws(self, action: torch.Tensor, reset_draws: torch.Tensor):
         """``step`` with injected reset draws ((N, 22) U[0,1): mirror, 21 joint noise) -- parity tests."""
         self._sim_step_counter += self.cfg.decimation
-        out = self._step_impl(action.to(self._device), reset_draws.to(self._device).float().contiguous())
+        action = action.to(self._device)
+        if self._action_terms is not None:  # as step(): process, the step, the manager's reset on the step's flags
+            action = self._action_terms.process(action)
+        out = self._step_impl(action, reset_draws.to(self._device).float().contiguous())
+        if self._action_terms is not None:
+            self._action_terms.reset(out[2], out[3])
         self._scene_changed()
         self._time_advanced()
         self.common_step_counter += 1
@@ -220,6 +226,8 @@ class AllstepsEnv(NativeDirectEnv):
     def physics_step(self, action: torch.Tensor):
         """Physics only (4 substeps, no task logic) -- known-answer tests / profiling."""
         a = action.to(self._device).float().contiguous()
+        if self._action_terms is not None:  # the physics reads the manager's commands
+            a = self._action_terms.process(a)
         self._native.physics_step(a, stream=self._stream())
         self._launches += 1
         self._scene_changed()

@@ -145,6 +145,15 @@ class AllstepsEnvCfg:
     # construction.  None: nothing is allocated or launched.
     terminations: object = None
     terminations_reset: bool = False
+    # Action manager (the reference's ManagerBasedEnvCfg `actions`): a dict or cfg object whose entries are
+    # utils.actions term cfgs, in cfg order (None entries are skipped), or None.  The walker's torque actuator
+    # serves JointEffortActionCfg terms that together command every joint exactly once: the processed action is
+    # the applied effort itself -- the hard-wired gain_curriculum * gear * clip(a) is not applied, so the
+    # curriculum gain does not act on an effort term.  The terms are processed on the device by k_actions_process
+    # (csrc/action_kernels.h), one launch per step ahead of the physics, as env.action_manager; action_space must
+    # equal the terms' total dimension.  Anything not served raises at construction.  None: nothing is allocated
+    # or launched and the step applies its own formula.
+    actions: object = None
 
     # joint gears, cfg/PhysX dof order (allsteps_env_cfg.py:133-155)
     joint_gears: list = field(default_factory=lambda: [

@@ -76,6 +76,7 @@ class AnymalCStonesEnv(NativeDirectEnv):
         # demand), as the walker's env serves them (envs/views.py)
         self.robot = _RobotView(self, default_joint_pos=self.default_joint_pos)
         self._actions = torch.zeros(n, self.num_dof, dtype=torch.float32, device=dev)
+        self._actions_start()
         self._observations_start()
         self._rewards_start()
         self._terminations_start()

@@ -131,6 +131,16 @@ class AnymalCStonesEnvCfg:
     # construction.  None: nothing is allocated or launched.
     terminations: object = None
     terminations_reset: bool = False
+    # Action manager (the reference's ManagerBasedEnvCfg `actions`): a dict or cfg object whose entries are
+    # utils.actions term cfgs, in cfg order (None entries are skipped), or None.  The quadruped's DC motor serves
+    # the joint position terms (JointPositionActionCfg, JointPositionToLimitsActionCfg,
+    # EMAJointPositionToLimitsActionCfg) that together command every joint exactly once: the processed action is
+    # the motor's position target itself -- the hard-wired default_q + action_scale * clip(a) is not applied.
+    # The terms are processed on the device by k_actions_process (csrc/action_kernels.h), one launch per step
+    # ahead of the physics, as env.action_manager; action_space must equal the terms' total dimension.  Anything
+    # not served raises at construction.  None: nothing is allocated or launched and the step applies its own
+    # formula.
+    actions: object = None
 
     # the stepping-stone task (authored; include/allsteps.h as_quad_task_t): the ALLSTEPS target
     # machine and reward terms (allsteps_env.py:347-394, 418-457) on four feet

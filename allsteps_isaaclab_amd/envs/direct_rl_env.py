@@ -49,6 +49,9 @@ class DirectRLEnv:
     # cfg.terminations (the reference's TerminationManager): the device state of the termination kernel, built by
     # _terminations_start once the subclass has its views.  None: step() launches nothing for it.
     _terminations = None
+    # cfg.actions (the reference's ActionManager): the device state of the action kernels, built by _actions_start
+    # once the subclass has its views and actuator.  None: step() launches nothing for it.
+    _action_terms = None
 
     def __init__(self, cfg, render_mode: str | None = None, **kwargs):
         self.cfg = cfg
@@ -167,15 +170,22 @@ class DirectRLEnv:
         above -- the reference's order, terminations first -- on the state as the step left it; they fill the
         manager's own buffers only, unless cfg.terminations_reset: then the envs the manager ends are reset by one
         masked reset, their observation rows and flags join the step's, and every later stage of this step sees the
-        merged flags, so those envs are reset once, in the usual places."""
+        merged flags, so those envs are reset once, in the usual places.  With cfg.actions: the action terms are
+        processed in one launch after the action noise model and before the physics, which reads their joint commands
+        in place of the actuator's own action formula; the manager's reset of the envs the step reset (and of those
+        cfg.terminations_reset ended) follows the step, on the device flags."""
         action = action.to(self._device)
         self._sim_step_counter += self.cfg.decimation
         nz = self._noise
         if nz is not None and nz.action is not None:
             action = nz.apply_actions(action, self._noise_offset(), self._noise_stream())
+        if self._action_terms is not None:
+            action = self._action_terms.process(action)
         out = self._step_impl(action)
         if self._terminations is not None:
             out = self._terminations.apply(out)
+        if self._action_terms is not None:
+            self._action_terms.reset(out[2], out[3])
         for sensor in self._lazy_sensors:  # (empty by default: the default step calls nothing)
             sensor.mark_dirty()
         if self._imus is not None:  # the step's sensor updates pass physics_dt (direct_rl_env.py:347)
@@ -257,6 +267,8 @@ class DirectRLEnv:
             self._observations.reset(mask)
         if self._rewards is not None:  # RewardManager.reset(env_ids): the episodic sums and prev_actions
             self._rewards.reset(mask)
+        if self._action_terms is not None:  # ActionManager.reset(env_ids): the action history, prev_applied
+            self._action_terms.reset(mask)
 
     # ------------------------------------------------------------------ interval events
     def _events_root_velocity(self):
@@ -361,6 +373,43 @@ class DirectRLEnv:
         if self._rewards is not None:
             self._rewards.set_state(state)
         return {k: v for k, v in state.items() if not EnvRewards.is_state_key(k)}
+
+    # ------------------------------------------------------------------ action manager
+    def _actions_start(self) -> None:
+        """Build the action manager of cfg.actions once the subclass has its views and actuator (its constructor
+        calls it ahead of _observations_start); raises NativeError for a cfg the kernels do not serve."""
+        from .actions import ActionManagerView, EnvActions
+
+        if EnvActions.wanted(self.cfg):
+            self._action_terms = EnvActions(self.cfg, self, self.num_envs, self._device)
+            self.action_manager = ActionManagerView(self._action_terms)
+            self._actions_attach(self._action_terms.cmd)
+            self._action_terms.reset(None)  # the envs stand reset: prev_applied = their joint positions
+
+    def _actions_context(self):
+        """The ActContext of the env: what its terms resolve against (subclass hook)."""
+        raise NotImplementedError(f"{type(self).__name__} does not serve cfg.actions")
+
+    def _actions_joint_pos(self) -> torch.Tensor:
+        """(joints, num_envs) the device rows of the joint positions, cfg dof order (subclass hook)."""
+        raise NotImplementedError(f"{type(self).__name__} does not serve cfg.actions")
+
+    def _actions_attach(self, cmd: torch.Tensor) -> None:
+        """Make the physics read its joint commands from ``cmd`` (N, joints) (subclass hook)."""
+        raise NotImplementedError(f"{type(self).__name__} does not serve cfg.actions")
+
+    def _actions_get_state(self) -> dict:
+        """The manager's action, prev_action, processed, prev_applied and the command buffer (no keys without
+        cfg.actions)."""
+        return {} if self._action_terms is None else self._action_terms.get_state()
+
+    def _actions_set_state(self, state: dict) -> dict:
+        """Load the action keys of a set_state dict; returns the dict without them."""
+        from .actions import EnvActions
+
+        if self._action_terms is not None:
+            self._action_terms.set_state(state)
+        return {k: v for k, v in state.items() if not EnvActions.is_state_key(k)}
 
     # ------------------------------------------------------------------ termination manager
     def _terminations_start(self) -> None:

@@ -115,7 +115,9 @@ class NativeDirectEnv(DirectRLEnv):
             default_joint_pos=d.default_joint_pos[0].detach().cpu().numpy(),
             default_joint_vel=d.default_joint_vel[0].detach().cpu().numpy(),
             soft_joint_pos_limits=d.soft_joint_pos_limits[0].detach().cpu().numpy(),
-            action_cols=int(self.cfg.action_space), clamp_actions=self._actions_clamped,
+            action_cols=int(self.cfg.action_space),
+            # (with cfg.actions last_action is the manager's `action`, which is not clamped)
+            clamp_actions=self._actions_clamped and self._action_terms is None,
             command_names=[] if self._commands is None else list(self._commands.terms.names),
             ray_sensors={} if hs is None else {"height_scanner": int(hs.num_rays)},
             imu_names=[] if self._imus is None else list(self._imus.sensors))
@@ -161,6 +163,24 @@ class NativeDirectEnv(DirectRLEnv):
                 "commands": None if cm is None or not len(cm.terms.names) else cm.vel.view(-1, self.num_envs),
                 "net": rep.forces()[1] if (net and rep is not None) else None,
                 "timers": None if tm is None else tm.timers}
+
+    def _actions_context(self):
+        from .actions import ActContext
+
+        d = self.robot.data
+        act = getattr(self._native, "_act", None)  # (set_actuator's; the walker never calls it: torque)
+        return ActContext(
+            joint_names=list(d.joint_names),
+            default_joint_pos=d.default_joint_pos[0].detach().cpu().numpy(),
+            soft_joint_pos_limits=d.soft_joint_pos_limits[0].detach().cpu().numpy(),
+            actuator=_native.ACT_TORQUE if act is None else int(act.mode),
+            action_space=int(self.cfg.action_space))
+
+    def _actions_joint_pos(self) -> torch.Tensor:
+        return self.state["q"][: int(self.model["num_hinges"])]
+
+    def _actions_attach(self, cmd: torch.Tensor) -> None:
+        self._native.set_joint_commands(cmd)
 
     def _terminations_context(self):
         from .terminations import SensorInfo, TermContext
@@ -225,11 +245,12 @@ class NativeDirectEnv(DirectRLEnv):
         actions (reward_episode_sums, reward_step, reward_last_episode_sums, reward_prev_actions); with
         cfg.terminations, the termination manager's flags (termination_term_dones, termination_last_episode_dones,
         (terms, N); termination_time_outs, termination_terminated, termination_dones, termination_reset_request,
-        (N,); uint8)."""
+        (N,); uint8); with cfg.actions, the action manager's buffers (action_action, action_prev_action,
+        action_processed, action_prev_applied, (N, columns); action_commands, (N, joints))."""
         tm, im = self._contact_timers, self._imus
         return {**{k: v.clone() for k, v in self.state.items()}, **self._noise_get_state(),
                 **self._events_get_state(), **self._commands_get_state(), **self._observations_get_state(),
-                **self._rewards_get_state(), **self._terminations_get_state(),
+                **self._rewards_get_state(), **self._terminations_get_state(), **self._actions_get_state(),
                 **({} if tm is None else tm.get_state()),
                 **({} if im is None else im.get_state())}
 
@@ -241,6 +262,7 @@ class NativeDirectEnv(DirectRLEnv):
             self._imus.set_state(state)
         state = {k: v for k, v in state.items() if k not in _ContactTimers.STATE_KEYS + _ImuSet.STATE_KEYS}
         state = self._terminations_set_state(self._rewards_set_state(self._observations_set_state(state)))
+        state = self._actions_set_state(state)
         for k, v in self._commands_set_state(self._events_set_state(self._noise_set_state(state))).items():
             self.state[k].copy_(torch.as_tensor(v).to(self.state[k].device, self.state[k].dtype).reshape(
                 self.state[k].shape))

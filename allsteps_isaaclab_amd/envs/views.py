@@ -914,4 +914,8 @@ def __getattr__(name: str):
         from .terminations import TerminationManagerView
 
         return TerminationManagerView
+    if name == "ActionManagerView":  # (``env.action_manager``, envs/actions.py: the same)
+        from .actions import ActionManagerView
+
+        return ActionManagerView
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

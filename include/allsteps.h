@@ -814,6 +814,52 @@ int as_terminations_step(const as_termination_term_t* terms, int32_t num_terms, 
                          uint8_t* terminated, uint8_t* dones, uint8_t* last_episode_dones, uint8_t* reset_request,
                          int32_t n, void* stream);
 
+/* Action manager, off by default: the joint action terms of cfg.actions (isaaclab/managers/action_manager.py, the
+ * terms of isaaclab/envs/mdp/actions: JointPositionAction, JointEffortAction, JointPositionToLimitsAction,
+ * EMAJointPositionToLimitsAction).  A column is one (term, joint) pair in cfg order.  as_actions_step is
+ * process_action: per (env, column) prev_action <- action, action <- input, processed <- the term's formula,
+ * prev_applied <- processed for an EMA column, cmd[env][joint] <- processed.  as_actions_reset is reset(env_ids) over
+ * the envs of mask | mask2 (both NULL: every env): action and prev_action are zeroed, an EMA column's prev_applied
+ * becomes q[joint][env].  The caller launches as_actions_step before as_step on the same stream and gives the step
+ * the command buffer with as_set_joint_commands.  Stateless entry points over caller-owned device buffers -- no
+ * as_env_t.  input, action, prev_action, processed and prev_applied are env-major [n][num_cols]; cmd is
+ * [n][cmd_cols] (cfg dof order) and q is field-major [cmd_cols][n].  Formulas and the float32 operations:
+ * csrc/allsteps_actions.h.  Graph-safe: the column descriptors are read from device memory at every launch; a
+ * column whose joint is outside [0, cmd_cols) stores no command and reads no q.  Symbols added only: AS_ABI_VERSION
+ * stays 6. */
+enum {
+  AS_ACTION_JOINT_POSITION = 0,       /* clamp(raw * scale + offset, clip)            a position target */
+  AS_ACTION_JOINT_EFFORT,             /* the same                                     an effort */
+  AS_ACTION_POSITION_TO_LIMITS,       /* clamp(raw * scale, clip), rescaled over the soft limits with rescale */
+  AS_ACTION_EMA_POSITION_TO_LIMITS,   /* the same, then the moving average over prev_applied, clamped to the limits */
+  AS_ACTION_NUM_KINDS
+};
+typedef struct {
+  int32_t joint;     /* the column's joint: its column of cmd and row of q (cfg dof order) */
+  int32_t kind;      /* AS_ACTION_* */
+  int32_t rescale;   /* != 0: rescale_to_limits */
+  int32_t term;      /* the term the column belongs to (informational) */
+  float scale, offset;
+  float clip_lo, clip_hi;  /* -inf / +inf without a clip */
+  float lim_lo, lim_hi;    /* the joint's soft position limits */
+  float alpha, one_minus_alpha;  /* both formed by the host as torch forms them */
+} as_action_column_t;
+/* cols [num_cols] is device memory, 1 <= num_cols <= AS_ACT_DIM, 1 <= cmd_cols <= AS_ACT_DIM.  NULL buffers and
+ * counts out of range are AS_ERR_INVALID before any device call. */
+int as_actions_step(const as_action_column_t* cols, int32_t num_cols, const float* input, float* action,
+                    float* prev_action, float* processed, float* prev_applied, float* cmd, int32_t cmd_cols,
+                    int32_t n, void* stream);
+int as_actions_reset(const as_action_column_t* cols, int32_t num_cols, float* action, float* prev_action,
+                     float* prev_applied, const float* q, int32_t q_rows, const uint8_t* mask, const uint8_t* mask2,
+                     int32_t n, void* stream);
+/* The seam in the physics step, a setup call like as_set_contact_report: with cmd_dev set, every later as_step,
+ * as_physics_step and as_quad_step reads joint j's command of env e at cmd_dev[e * num_hinges + j] (cfg dof order)
+ * in place of the actuator's own formula -- in AS_ACT_TORQUE the applied effort is the command itself (no curriculum
+ * gain, no gear, no clip), in AS_ACT_DC_MOTOR the position target is the command itself.  The task epilogues keep
+ * reading the clamped raw action.  Reset and task-only launches ignore it.  NULL switches it off.  The buffer is
+ * caller-owned and must stay alive. */
+int as_set_joint_commands(as_env_t* env, const float* cmd_dev);
+
 /* The H^-1 sweep plan for a model (round 6, ABI 5; no device needed). The step kernel sweeps the
  * padded joint-space inertia last block first and, for the trees it is compiled for (the walker, the
  * C5 quadruped), skips the column quads in which the pivot rows are structurally zero -- an exact
