@@ -30,7 +30,7 @@ EXPORTED_SYMBOLS = [
     "as_contact_timers", "as_ray_cast", "as_imu", "as_ray_camera",
     "as_frame_transformer", "as_commands_step", "as_commands_reset", "as_observations_step",
     "as_observations_reset", "as_rewards_step", "as_rewards_reset", "as_terminations_step",
-    "as_actions_step", "as_actions_reset", "as_set_joint_commands",
+    "as_actions_step", "as_actions_reset", "as_set_joint_commands", "as_quad_reset_mask",
 ]
 MAXB = 32  # AS_MAX_BODIES
 MAXC = 10  # AS_MAX_CONTACTS
@@ -550,6 +550,7 @@ def load() -> C.CDLL:
     L.as_set_quad_task.argtypes = [V, V]
     L.as_quad_step.argtypes = [V, V, V, V, V, V, V]
     L.as_quad_reset_all.argtypes = [V, V, V]
+    L.as_quad_reset_mask.argtypes = [V, V, V, V]
     L.as_body_state.argtypes = [V, V, V, V]
     L.as_sweep_plan.argtypes = [V, C.POINTER(C.c_uint64)]
     L.as_set_contact_report.argtypes = [V, V]
@@ -865,6 +866,10 @@ class NativeEnv:
 
     def quad_reset_all(self, obs, stream=None):
         check(self.L.as_quad_reset_all(self.h, obs.data_ptr(), stream), "as_quad_reset_all")
+
+    def quad_reset_mask(self, mask, obs, stream=None):
+        """as_quad_reset_mask: mask (n,) uint8 on the device; only the masked envs' rows of obs are written."""
+        check(self.L.as_quad_reset_mask(self.h, mask.data_ptr(), obs.data_ptr(), stream), "as_quad_reset_mask")
 
     def generate_stones(self, level: int, draws=None, stream=None):
         check(self.L.as_generate_stones(self.h, level, _ptr(draws), stream), "as_generate_stones")

@@ -417,8 +417,9 @@ int as_set_quad_task(as_env_t* env, const as_quad_task_t* q) {
   return AS_OK;
 }
 
+// reset_all with a mask: the masked reset (k_quad_reset_mask), which touches the masked envs only
 static int quad(as_env_t* env, int reset_all, const float* actions, float* obs, float* reward, uint8_t* term,
-                uint8_t* trunc, void* stream) {
+                uint8_t* trunc, void* stream, const uint8_t* mask = nullptr) {
   if (!env->quad_ready) return fail(AS_ERR_INVALID, "as_quad_*: call as_set_quad_task first");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   if (!reset_all) {
@@ -441,7 +442,8 @@ static int quad(as_env_t* env, int reset_all, const float* actions, float* obs, 
   a.wave_map = env->wave_map_dev;
   a.map_streamed = env->map_streamed;
   a.rep = env->report.count ? env->report_dev : nullptr;
-  HIP_TRY(as::launch_quad(a, s));
+  if (mask) HIP_TRY(as::launch_quad_reset_mask(a, mask, s));
+  else HIP_TRY(as::launch_quad(a, s));
   return AS_OK;
 }
 
@@ -455,6 +457,11 @@ int as_quad_step(as_env_t* env, const float* actions, float* obs, float* reward,
 int as_quad_reset_all(as_env_t* env, float* obs, void* stream) {
   if (!env || !obs) return fail(AS_ERR_INVALID, "as_quad_reset_all: null argument");
   return quad(env, 1, nullptr, obs, nullptr, nullptr, nullptr, stream);
+}
+
+int as_quad_reset_mask(as_env_t* env, const uint8_t* mask, float* obs, void* stream) {
+  if (!env || !mask || !obs) return fail(AS_ERR_INVALID, "as_quad_reset_mask: null argument");
+  return quad(env, 1, nullptr, obs, nullptr, nullptr, nullptr, stream, mask);
 }
 
 int as_generate_stones(as_env_t* env, int32_t level, const float* draws, void* stream) {

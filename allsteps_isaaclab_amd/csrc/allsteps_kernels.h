@@ -403,6 +403,9 @@ hipError_t launch_step(const StepArgs& a, int nv, bool sweep_skip, hipStream_t s
 hipError_t launch_obs(const ObsArgs& a, hipStream_t stream);
 hipError_t launch_stones(const StonesArgs& a, hipStream_t stream);
 hipError_t launch_quad(const QuadArgs& a, hipStream_t stream);
+// k_quad's reset path for the envs of a device mask [n] (uint8), nothing for the others; a.reset_all, a.actions,
+// a.reward, a.terminated, a.truncated, a.side, a.wave_map are not read
+hipError_t launch_quad_reset_mask(const QuadArgs& a, const uint8_t* mask, hipStream_t stream);
 // zero n int32 words with a kernel (graph-safe stepping: a kernel node instead of a memset node)
 hipError_t launch_zero(int32_t* p, int n, hipStream_t stream);
 size_t step_lds_bytes();

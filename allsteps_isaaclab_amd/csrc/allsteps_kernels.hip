@@ -523,7 +523,13 @@ hipError_t launch_stones(const StonesArgs& a, hipStream_t stream) {
 }
 
 hipError_t launch_quad(const QuadArgs& a, hipStream_t stream) {
-  hipLaunchKernelGGL(k_quad, dim3((a.n + kQuadEnvs - 1) / kQuadEnvs), dim3(4 * kQuadEnvs), 0, stream, a);
+  hipLaunchKernelGGL(k_quad<false>, dim3((a.n + kQuadEnvs - 1) / kQuadEnvs), dim3(4 * kQuadEnvs), 0, stream, a,
+                     (const uint8_t*)nullptr);
+  return hipGetLastError();
+}
+
+hipError_t launch_quad_reset_mask(const QuadArgs& a, const uint8_t* mask, hipStream_t stream) {
+  hipLaunchKernelGGL(k_quad<true>, dim3((a.n + kQuadEnvs - 1) / kQuadEnvs), dim3(4 * kQuadEnvs), 0, stream, a, mask);
   return hipGetLastError();
 }
 

@@ -169,7 +169,15 @@ struct QuadSmem {
   float obs[kQuadEnvs][AS_QUAD_OBS_DIM + 1];  // observation rows, written out coalesced (+1: banks)
 };
 
-__global__ __launch_bounds__(4 * kQuadEnvs) void k_quad(QuadArgs P) {
+// The mode is a compile-time parameter.  k_quad<false> is the step (or, with P.reset_all, the reset of every
+// env) and never reads `mask`; its instruction stream is that of the kernel without the parameter.
+// k_quad<true> is the masked reset (as_quad_reset_mask): the reset_all path for the envs whose mask byte
+// ([n] uint8) is set and nothing at all for the others -- an unmasked env is not live (no load, no store;
+// tail lanes do not read the mask), phase 3 skips it and the write-out copies only the reset envs' rows.
+// It leaves the wave map alone: only k_step writes the cost rows the map is ranked by, so a rebuild here
+// would reproduce the map that stands.
+template <bool kMasked>
+__global__ __launch_bounds__(4 * kQuadEnvs) void k_quad(QuadArgs P, const uint8_t* mask) {
   const Consts& K = *(const Consts*)(CK*)P.consts;
   const as_model_t& m = K.model;
   const as_quad_task_t& Q = K.quad;
@@ -178,7 +186,8 @@ __global__ __launch_bounds__(4 * kQuadEnvs) void k_quad(QuadArgs P) {
   const int n = P.n, nh = m.num_hinges, N = K.task.num_steps;
   const as_state_t& st = P.st;
   static_assert(kQuadEnvs == kMapEnvs, "a workgroup's envs are one placement chunk");
-  if (P.wave_map && tid < kMapEnvs) build_wave_map(P.side, P.wave_map, n, P.map_streamed != 0, blockIdx.x, tid);  // (wave 0)
+  if (!kMasked && P.wave_map && tid < kMapEnvs)
+    build_wave_map(P.side, P.wave_map, n, P.map_streamed != 0, blockIdx.x, tid);  // (wave 0)
   // ---- the model tables of the feet's chains, once per workgroup
   if (tid == 0) as_link_dof_map(m.cfg_dof_link, nh, AS_MAX_LINKS, qs.link_dof);
   if (tid < AS_MAX_LINKS) {
@@ -207,7 +216,7 @@ __global__ __launch_bounds__(4 * kQuadEnvs) void k_quad(QuadArgs P) {
   // ---- (1) tips of the stepped state, thread = (env, foot)
   {
     const int le = tid >> 2, f = tid & 3, e = blockIdx.x * kQuadEnvs + le;
-    if (!P.reset_all && e < n) {
+    if (!(kMasked || P.reset_all) && e < n) {
       float rp[3], rq[4];
       for (int k = 0; k < 3; ++k) rp[k] = st.root_pos[k * n + e];
       for (int k = 0; k < 4; ++k) rq[k] = st.root_quat[k * n + e];
@@ -217,7 +226,8 @@ __global__ __launch_bounds__(4 * kQuadEnvs) void k_quad(QuadArgs P) {
   __syncthreads();
   // ---- (2) task logic, thread = env
   const int le = tid, e = blockIdx.x * kQuadEnvs + le;
-  const bool live = tid < kQuadEnvs && e < n;
+  bool live = tid < kQuadEnvs && e < n;
+  if (kMasked) live = live && mask[e] != 0;
   auto stone = [&](int k, int c) { return st.stones[(3 * k + c) * n + e]; };
   // xy distance of foot f's tip to the aim point on stone k
   auto aim_dist = [&](int f, int k, const float* tip) {
@@ -237,7 +247,7 @@ __global__ __launch_bounds__(4 * kQuadEnvs) void k_quad(QuadArgs P) {
     }
     for (int k = 0; k < 4; ++k) rq[k] = st.root_quat[k * n + e];
     for (int k = 0; k < nh; ++k) {
-      const float x = P.reset_all ? 0.f : P.actions[(size_t)e * nh + k];
+      const float x = (kMasked || P.reset_all) ? 0.f : P.actions[(size_t)e * nh + k];
       a[k] = fminf(fmaxf(x, -1.f), 1.f);
     }
     idx = st.idx[e];
@@ -254,7 +264,7 @@ __global__ __launch_bounds__(4 * kQuadEnvs) void k_quad(QuadArgs P) {
     pot = st.pot[e];
     old_pot = st.old_pot[e];
     bool term = false, trunc = false;
-    if (!P.reset_all) {
+    if (!(kMasked || P.reset_all)) {
       ep_len += 1;
       // target tick per foot (allsteps_env.py:418-440) and the step reward of a fresh reach (:377-380)
       float step_hit = 0.f, fsum = 0.f;
@@ -296,7 +306,7 @@ __global__ __launch_bounds__(4 * kQuadEnvs) void k_quad(QuadArgs P) {
       q[k] = st.q[k * n + e];
       qd[k] = st.qd[k * n + e];
     }
-    was_reset = P.reset_all || term || trunc;
+    was_reset = kMasked || P.reset_all || term || trunc;
     if (was_reset) {
       // the stand pose over stones 0 (hind feet) and 1 (front feet), joints + U(-1, 1) * noise
       float blk[4];
@@ -396,7 +406,7 @@ __global__ __launch_bounds__(4 * kQuadEnvs) void k_quad(QuadArgs P) {
   const int e0 = blockIdx.x * kQuadEnvs, rows = min(kQuadEnvs, n - e0);
   float* ob = P.obs + (size_t)e0 * AS_QUAD_OBS_DIM;
   for (int x = tid; x < rows * AS_QUAD_OBS_DIM; x += 4 * kQuadEnvs)
-    ob[x] = qs.obs[x / AS_QUAD_OBS_DIM][x % AS_QUAD_OBS_DIM];
+    if (!kMasked || qs.reset[x / AS_QUAD_OBS_DIM]) ob[x] = qs.obs[x / AS_QUAD_OBS_DIM][x % AS_QUAD_OBS_DIM];
 }
 
 }  // namespace as

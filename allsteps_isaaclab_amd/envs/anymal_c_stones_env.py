@@ -29,7 +29,7 @@ class AnymalCStonesEnv(NativeDirectEnv):
     cfg: AnymalCStonesEnvCfg
 
     def __init__(self, cfg: AnymalCStonesEnvCfg | None = None, render_mode: str | None = None, *,
-                 contact_forces: bool | None = None, **kwargs):
+                 env_id_offset: int = 0, contact_forces: bool | None = None, **kwargs):
         cfg = cfg or AnymalCStonesEnvCfg()
         super().__init__(cfg, render_mode, **kwargs)
         model = load_model(ANYMAL_C_JSON)
@@ -39,7 +39,8 @@ class AnymalCStonesEnv(NativeDirectEnv):
         if self.num_dof != cfg.action_space:
             raise ValueError(f"model has {self.num_dof} hinges, cfg.action_space = {cfg.action_space}")
         # the opt-in contact report (cfg.contact_forces) comes with the handle
-        self._init_native(model, hind=True, feet=True, contact_forces=contact_forces)
+        # env_id_offset: a shard's first global env id, the key of the reset draws (as AllstepsEnv's)
+        self._init_native(model, hind=True, feet=True, env_id_offset=env_id_offset, contact_forces=contact_forces)
         n, dev = self.num_envs, self._device
         self.state["stones"][:] = torch.as_tensor(level0_stones(n, cfg.num_steps), device=dev)
         self.default_joint_pos = torch.as_tensor(stand_pose(model["dof_names"], cfg.robot.init_joint_pos), device=dev)
@@ -125,6 +126,35 @@ class AnymalCStonesEnv(NativeDirectEnv):
         self._native.quad_reset_all(self.obs_buf, stream=self._stream())
         self._launches += 1
         self._reset_buf_stale = True
+        return {"policy": self.obs_buf}
+
+    def _reset_idx(self, env_ids):
+        """AnymalCEnv._reset_idx(env_ids) (anymal_c_env.py:163-182): reset the given envs -- ``as_quad_reset_mask``
+        on a device mask, one launch, no physics -- and rewrite their rows of ``obs_buf`` in place; the other
+        envs keep their state and the last step's observation.  ``env_ids``: indices, a bool mask of shape
+        (num_envs,), or None (all envs).  The stateful sensors, the managers and the noise models reset the same
+        envs; ``reset_terminated`` / ``reset_time_outs`` and ``reset_buf`` stay as they are."""
+        self._scene_changed()
+        if env_ids is None:
+            obs = self._reset_impl()
+            self._sensors_reset(None)
+            self._noise_reset(None)
+            return obs
+        ids = torch.as_tensor(env_ids, device=self._device)
+        if ids.dtype == torch.bool:
+            if ids.shape != (self.num_envs,):
+                raise ValueError(f"env_ids mask must be ({self.num_envs},), got {tuple(ids.shape)}")
+            mask = ids.to(torch.uint8).contiguous()
+        else:
+            ids = ids.long().reshape(-1)
+            if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= self.num_envs):
+                raise IndexError(f"env_ids out of range [0, {self.num_envs})")
+            mask = torch.zeros(self.num_envs, dtype=torch.uint8, device=self._device)
+            mask[ids] = 1
+        self._native.quad_reset_mask(mask, self.obs_buf, stream=self._stream())
+        self._launches += 1  # (the masked envs' report counts were cleared)
+        self._sensors_reset(mask)
+        self._noise_reset(mask)
         return {"policy": self.obs_buf}
 
     def _step_impl(self, action: torch.Tensor):

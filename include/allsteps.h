@@ -271,6 +271,14 @@ int as_set_quad_task(as_env_t* env, const as_quad_task_t* task_host);
 int as_quad_step(as_env_t* env, const float* actions, float* obs, float* reward, uint8_t* terminated,
                  uint8_t* truncated, void* stream);
 int as_quad_reset_all(as_env_t* env, float* obs, void* stream);
+/* AnymalCEnv._reset_idx(env_ids): as_quad_reset_all's reset for the envs with mask[e] != 0 (mask: [n] uint8,
+ * device) -- stand pose + the env's next Philox joint-noise draw, episode + 1, targets, potentials, ep_len,
+ * contact masks and contact-report counts cleared -- in one launch without physics, host synchronisation or
+ * atomics; the mask is read on `stream`, so the call can be captured and the mask rewritten between replays.
+ * Of obs [n][AS_QUAD_OBS_DIM] only the masked envs' rows are written (action columns zero); an env with
+ * mask[e] == 0 keeps its state, masks, report and obs row untouched.  Null arguments, or a call before
+ * as_set_quad_task: AS_ERR_INVALID. */
+int as_quad_reset_mask(as_env_t* env, const uint8_t* mask, float* obs, void* stream);
 
 /* _generate_foot_steps_allsteps (allsteps_env.py:125-174) on the device at curriculum `level`;
  * draws: [5][n][20] U[0,1) (NULL = Philox stream (seed, env, 0xF007)). Writes state->stones. */
@@ -317,8 +325,8 @@ int as_body_state(as_env_t* env, const as_body_table_t* bodies_host, float* out,
  *   qd_prev [AS_ACT_DIM][n]   joint velocities (cfg dof order) at the start of the launch's last substep:
  *                             joint_acc = (qd - qd_prev) / dt
  * Launches without physics (as_reset_*, as_task_step) leave the report as it is, and an env that as_step
- * resets keeps its last substep's records exactly as it keeps its contact_mask; as_quad_step / as_quad_reset_all,
- * which clear a reset env's masks, clear its counts.
+ * resets keeps its last substep's records exactly as it keeps its contact_mask; as_quad_step / as_quad_reset_all /
+ * as_quad_reset_mask, which clear a reset env's masks, clear its counts.
  * as_set_contact_report is a setup call like as_debug_stamps (not during graph capture): the pointers are
  * stored and every later launch writes through them, a replayed graph included.  1 <= depth <=
  * sim.substeps, else AS_ERR_INVALID; report == NULL switches the report off. */
