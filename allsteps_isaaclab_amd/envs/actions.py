@@ -22,9 +22,8 @@ import torch
 
 from .. import _native
 from ..utils import actions as AC
+from ._manager import DeviceState, cfg_items, u8
 
-STATE_PREFIX = "action_"
-STATE_NAMES = ("action", "prev_action", "processed", "prev_applied", "commands")
 KIND_POSITION, KIND_EFFORT, KIND_TO_LIMITS, KIND_EMA = range(4)  # AS_ACTION_*
 _POSITION_KINDS = (KIND_POSITION, KIND_TO_LIMITS, KIND_EMA)
 # words of as_action_column_t
@@ -63,17 +62,9 @@ class ActionTerm:
 
 
 def named_terms(actions) -> list:
-    """[(name, cfg)] of a dict or cfg object, in its order, without the None entries."""
-    items = actions.items() if isinstance(actions, dict) else vars(actions).items()
-    out = []
-    for name, c in items:
-        if c is None:
-            continue
-        if not isinstance(c, AC.ActionTermCfg):
-            raise TypeError(f"Configuration for the term '{name}' is not of type ActionTermCfg. Received: "
-                            f"'{type(c)}'.")
-        out.append((name, c))
-    return out
+    """[(name, cfg)] of a dict or cfg object, in its order, without the None entries.  Unlike the other managers'
+    walks this one has never read a class's attributes or passed over names that begin with ``_``; it is kept so."""
+    return list(cfg_items(actions, AC.ActionTermCfg, private="keep", class_attrs=False))
 
 
 def _f32(x) -> np.float32:
@@ -235,8 +226,10 @@ class ActionTerms:
         return msg + "".join(fmt(r) for r in rows) + line
 
 
-class EnvActions:
+class EnvActions(DeviceState):
     """The actions side of a DirectRLEnv: the device column table, the manager's buffers and the command buffer."""
+
+    STATE_KEYS = ("action_action", "action_prev_action", "action_processed", "action_prev_applied", "action_commands")
 
     def __init__(self, cfg, env, n: int, device):
         self.n, self.device = n, device
@@ -252,10 +245,6 @@ class EnvActions:
     @staticmethod
     def wanted(cfg) -> bool:
         return getattr(cfg, "actions", None) is not None
-
-    @staticmethod
-    def is_state_key(k: str) -> bool:
-        return k.startswith(STATE_PREFIX) and k[len(STATE_PREFIX):] in STATE_NAMES
 
     # ---- launches
     def process(self, action: torch.Tensor) -> torch.Tensor:
@@ -278,29 +267,14 @@ class EnvActions:
         """ActionManager.reset over the envs of mask | mask2 ((n,) uint8 / bool device tensors; neither: all): one
         stream-ordered launch, no host read."""
         q = self._env._actions_joint_pos()
-        _native.actions_reset(self.cols, self.action, self.prev_action, self.prev_applied, q, _u8(mask), _u8(mask2),
+        _native.actions_reset(self.cols, self.action, self.prev_action, self.prev_applied, q, u8(mask), u8(mask2),
                               stream=self._env._noise_stream())
         self.launches += 1
 
     # ---- state (get_state / set_state of the envs)
     def tensors(self) -> dict:
-        return {STATE_PREFIX + k: v for k, v in zip(STATE_NAMES, (self.action, self.prev_action, self.processed,
-                                                                  self.prev_applied, self.cmd))}
-
-    def get_state(self) -> dict:
-        return {k: v.clone() for k, v in self.tensors().items()}
-
-    def set_state(self, state: dict) -> None:
-        for k, v in self.tensors().items():
-            if k in state:
-                v.copy_(torch.as_tensor(state[k]).to(v.device, v.dtype).reshape(v.shape))
-
-
-def _u8(x):
-    if x is None:
-        return None
-    x = x.view(torch.uint8) if x.dtype == torch.bool else x.to(torch.uint8)
-    return x.contiguous()
+        return dict(zip(self.STATE_KEYS, (self.action, self.prev_action, self.processed, self.prev_applied,
+                                          self.cmd)))
 
 
 class ActionTermView:

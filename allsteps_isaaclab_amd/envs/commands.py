@@ -19,6 +19,7 @@ import torch
 
 from .. import _native
 from ..utils import commands as CM
+from ._manager import DeviceState, RowTerms, is_number, u8
 
 METRIC_NAMES = ("error_vel_xy", "error_vel_yaw")
 
@@ -28,16 +29,12 @@ def _unsupported(term: str, detail: str) -> "_native.NativeError":
                                f"fallback); supported: {CM.SUPPORTED}")
 
 
-def _is_number(x) -> bool:
-    return isinstance(x, (int, float, np.floating, np.integer)) and not isinstance(x, bool)
-
-
 def _tuple(x, k: int, term: str, what: str) -> tuple:
     try:
         vals = tuple(x)
     except TypeError:
         raise _unsupported(term, f"{what} = {x!r} is not a tuple of {k} numbers") from None
-    if len(vals) != k or not all(_is_number(v) for v in vals):
+    if len(vals) != k or not all(is_number(v) for v in vals):
         raise _unsupported(term, f"{what} = {x!r} is not a tuple of {k} numbers")
     return tuple(float(v) for v in vals)
 
@@ -50,7 +47,7 @@ def _range(x, term: str, what: str) -> tuple[float, float]:
 
 
 def _prob(x, term: str, what: str) -> np.float32:
-    if not _is_number(x):
+    if not is_number(x):
         raise _unsupported(term, f"{what} = {x!r} is not a number")
     return np.float32(x)
 
@@ -113,7 +110,7 @@ def term_row(name: str, cfg, step_dt: float) -> np.ndarray:
             row[8 + k] = f(hi) - f(lo)
         ints[1] = 1 if cfg.heading_command else 0
         row[12], row[13] = (f(v) for v in _range(ranges.ang_vel_z, name, "ranges.ang_vel_z"))
-        if not _is_number(cfg.heading_control_stiffness):
+        if not is_number(cfg.heading_control_stiffness):
             raise _unsupported(name, f"heading_control_stiffness = {cfg.heading_control_stiffness!r} is not a number")
         row[14] = f(cfg.heading_control_stiffness)
         row[15] = _prob(cfg.rel_heading_envs, name, "rel_heading_envs")
@@ -125,57 +122,22 @@ def term_row(name: str, cfg, step_dt: float) -> np.ndarray:
     return row
 
 
-def parse_terms(commands) -> list[tuple[str, object]]:
-    """(name, CommandTermCfg) of cfg.commands in cfg order: a dict, or an object whose attributes are the terms
-    (the reference's configclass; a plain class's class attributes count too).  None entries are skipped
-    (command_manager.py:409-410)."""
-    if isinstance(commands, dict):
-        items = list(commands.items())
-    else:
-        items = list(vars(commands).items())
-        seen = {k for k, _ in items}
-        for klass in reversed(type(commands).__mro__[:-1]):
-            items += [(k, v) for k, v in vars(klass).items()
-                      if k not in seen and not k.startswith("_") and isinstance(v, CM.CommandTermCfg)]
-            seen |= {k for k, _ in items}
-    out = []
-    for name, term in items:
-        if term is None or name.startswith("_"):
-            continue
-        if not isinstance(term, CM.CommandTermCfg):
-            raise TypeError(f"Configuration for the term '{name}' is not of type CommandTermCfg. Received: "
-                            f"'{type(term)}'.")
-        out.append((name, term))
-    return out
+class CommandTerms(RowTerms):
+    """The host side of cfg.commands: names, cfgs and descriptor rows, checked (no device needed).  None entries
+    are skipped (command_manager.py:409-410)."""
 
-
-class CommandTerms:
-    """The host side of cfg.commands: names, cfgs and descriptor rows, checked (no device needed)."""
+    NOUN, TERM_TYPE, WORDS = "command", CM.CommandTermCfg, _native.COMMAND_TERM_WORDS
+    LIMIT = ("AS_MAX_COMMAND_TERMS", _native.MAX_COMMAND_TERMS)
 
     def __init__(self, commands, step_dt: float):
-        terms = parse_terms(commands)
-        if len(terms) > _native.MAX_COMMAND_TERMS:
-            raise _native.NativeError(f"cfg.commands has {len(terms)} terms ({[k for k, _ in terms]}); the command "
-                                      f"kernel takes at most AS_MAX_COMMAND_TERMS = {_native.MAX_COMMAND_TERMS}")
         self.step_dt = float(step_dt)
-        self.names = [k for k, _ in terms]
-        self.cfgs = [c for _, c in terms]
-        self.rows = np.stack([term_row(k, c, self.step_dt) for k, c in terms]) if terms else \
-            np.zeros((0, _native.COMMAND_TERM_WORDS), np.float32)
+        super().__init__(commands)
 
-    def index(self, term_name: str) -> int:
-        if term_name not in self.names:
-            raise ValueError(f"Command term '{term_name}' not found.")
-        return self.names.index(term_name)
-
-    def set(self, term_name: str, cfg) -> int:
-        k = self.index(term_name)
-        self.rows[k] = term_row(term_name, cfg, self.step_dt)
-        self.cfgs[k] = cfg
-        return k
+    def row(self, name: str, cfg) -> np.ndarray:
+        return term_row(name, cfg, self.step_dt)
 
 
-class EnvCommands:
+class EnvCommands(DeviceState):
     """The commands side of a DirectRLEnv: term descriptors, the terms' per-env state and the stream counter."""
 
     STATE_KEYS = ("command_t", "command_time_left", "command_vel_b", "command_heading_target", "command_flags",
@@ -218,8 +180,7 @@ class EnvCommands:
         if not len(self.terms.names):
             return
         if mask is not None:
-            mask = mask.to(self.device).reshape(self.n)
-            mask = mask.view(torch.uint8) if mask.dtype == torch.bool else mask.to(torch.uint8)
+            mask = u8(mask.to(self.device).reshape(self.n))
         _native.commands_reset(self.desc, *self._state_args(), mask=mask, seed=self.seed, env_offset=env_offset,
                                stream=stream)
 
@@ -236,14 +197,6 @@ class EnvCommands:
     def tensors(self) -> dict:
         return dict(zip(self.STATE_KEYS, (self.t, self.time_left, self.vel, self.heading_target, self.flags,
                                           self.counter, self.metrics, self.last_metrics)))
-
-    def get_state(self) -> dict:
-        return {k: v.clone() for k, v in self.tensors().items()}
-
-    def set_state(self, state: dict) -> None:
-        for k, v in self.tensors().items():
-            if k in state:
-                v.copy_(torch.as_tensor(state[k]).to(v.device, v.dtype).reshape(v.shape))
 
 
 class CommandTermView:

@@ -10,12 +10,28 @@ Omniverse simulation context: a subclass owns a native step backend and implemen
 from __future__ import annotations
 
 import math
+from functools import partialmethod
 from typing import Any
 
 import torch
 
 from .scene import SceneView
 from .spaces import Box, Dict, batch_box
+
+
+def _part_classes() -> dict:
+    """{attribute of the env: class} of every part of an env that carries device state from step to step, in the
+    order of get_state's keys (the parts are built in another order: the actions ahead of the observations)."""
+    from .actions import EnvActions
+    from .commands import EnvCommands
+    from .events import EnvEvents
+    from .noise import EnvNoise
+    from .observations import EnvObservations
+    from .rewards import EnvRewards
+    from .terminations import EnvTerminations
+
+    return {"_noise": EnvNoise, "_events": EnvEvents, "_commands": EnvCommands, "_observations": EnvObservations,
+            "_rewards": EnvRewards, "_terminations": EnvTerminations, "_action_terms": EnvActions}
 
 
 class DirectRLEnv:
@@ -40,6 +56,9 @@ class DirectRLEnv:
     # outdated by time and by reset only, env by env (a recompute moves their previous velocities).  None: nothing
     # to mark.
     _imus = None
+    # cfg.action_noise_model / cfg.observation_noise_model, cfg.events, cfg.commands: the device state of their
+    # kernels, built by the constructor.  None: step() launches nothing for them and nothing is allocated.
+    _noise = _events = _commands = None
     # cfg.observations (the reference's ObservationManager): the device state of the observation kernel, built by
     # _observations_start once the subclass has its views.  None: step() launches nothing for it.
     _observations = None
@@ -221,17 +240,43 @@ class DirectRLEnv:
         if self._noise is not None:
             self._noise.post(None, mask, None, self._noise_offset(), self._noise_stream())
 
-    def _noise_get_state(self) -> dict:
-        """The noise stream's counter and biases for get_state (no keys without a model)."""
-        return {} if self._noise is None else self._noise.get_state()
+    # ------------------------------------------------------------------ state of the parts
+    def _part_get_state(self, attr: str) -> dict:
+        """The state keys of the part under ``attr`` (a key of _part_classes); none where the env has no such part."""
+        part = getattr(self, attr)
+        return {} if part is None else part.get_state()
 
-    def _noise_set_state(self, state: dict) -> dict:
-        """Load the noise keys of a set_state dict; returns the dict without them."""
-        from .noise import EnvNoise
+    def _part_set_state(self, attr: str, state: dict) -> dict:
+        """Load the part's keys of a set_state dict; returns the dict without the keys the part's class owns --
+        whether or not the env has the part, so a key of a manager the env was built without is dropped."""
+        part, owns = getattr(self, attr), _part_classes()[attr].owns
+        if part is not None:
+            part.set_state(state)
+        return {k: v for k, v in state.items() if not owns(k)}
 
-        if self._noise is not None:
-            self._noise.set_state(state)
-        return {k: v for k, v in state.items() if k not in EnvNoise.STATE_KEYS}
+    def _parts_get_state(self) -> dict:
+        """The state of every part the env has, merged."""
+        out = {}
+        for attr in _part_classes():
+            out.update(self._part_get_state(attr))
+        return out
+
+    def _parts_set_state(self, state: dict) -> dict:
+        """Hand every part the env has a set_state dict; returns the dict without the keys of any part class."""
+        for attr in _part_classes():
+            state = self._part_set_state(attr, state)
+        return state
+
+    # One part's half of the two calls above, under the per-manager names that callers outside this class use.
+    _events_get_state = partialmethod(_part_get_state, "_events")
+    _commands_get_state = partialmethod(_part_get_state, "_commands")
+    _commands_set_state = partialmethod(_part_set_state, "_commands")
+    _rewards_get_state = partialmethod(_part_get_state, "_rewards")
+    _rewards_set_state = partialmethod(_part_set_state, "_rewards")
+    _terminations_get_state = partialmethod(_part_get_state, "_terminations")
+    _terminations_set_state = partialmethod(_part_set_state, "_terminations")
+    _actions_get_state = partialmethod(_part_get_state, "_action_terms")
+    _actions_set_state = partialmethod(_part_set_state, "_action_terms")
 
     # ------------------------------------------------------------------ lazy sensors
     def _add_lazy_sensor(self, sensor, camera: bool = False) -> None:
@@ -280,35 +325,11 @@ class DirectRLEnv:
         if self._events is not None:
             self._events.start(self._noise_offset(), self._noise_stream())
 
-    def _events_get_state(self) -> dict:
-        """The event streams' counter and timers for get_state (no keys without cfg.events)."""
-        return {} if self._events is None else self._events.get_state()
-
-    def _events_set_state(self, state: dict) -> dict:
-        """Load the event keys of a set_state dict; returns the dict without them."""
-        from .events import EnvEvents
-
-        if self._events is not None:
-            self._events.set_state(state)
-        return {k: v for k, v in state.items() if k not in EnvEvents.STATE_KEYS}
-
     # ------------------------------------------------------------------ command manager
     def _commands_root_state(self):
         """(root_quat (4, n), root_lin (3, n), root_ang (3, n)): the device rows the command terms read (subclass
         hook)."""
         raise NotImplementedError(f"{type(self).__name__} does not expose a root state for cfg.commands")
-
-    def _commands_get_state(self) -> dict:
-        """The command streams' counter and the terms' state for get_state (no keys without cfg.commands)."""
-        return {} if self._commands is None else self._commands.get_state()
-
-    def _commands_set_state(self, state: dict) -> dict:
-        """Load the command keys of a set_state dict; returns the dict without them."""
-        from .commands import EnvCommands
-
-        if self._commands is not None:
-            self._commands.set_state(state)
-        return {k: v for k, v in state.items() if k not in EnvCommands.STATE_KEYS}
 
     # ------------------------------------------------------------------ observation manager
     def _observations_start(self) -> None:
@@ -329,19 +350,6 @@ class DirectRLEnv:
         """{source name: device tensor} of the rows the terms read (subclass hook)."""
         raise NotImplementedError(f"{type(self).__name__} does not serve cfg.observations")
 
-    def _observations_get_state(self) -> dict:
-        """The observation streams' counters, the push counts and the histories (no keys without
-        cfg.observations)."""
-        return {} if self._observations is None else self._observations.get_state()
-
-    def _observations_set_state(self, state: dict) -> dict:
-        """Load the observation keys of a set_state dict; returns the dict without them."""
-        from .observations import EnvObservations
-
-        if self._observations is not None:
-            self._observations.set_state(state)
-        return {k: v for k, v in state.items() if not EnvObservations.is_state_key(k)}
-
     # ------------------------------------------------------------------ reward manager
     def _rewards_start(self) -> None:
         """Build the reward manager of cfg.rewards once the subclass has its state, views and sensors (its
@@ -360,19 +368,6 @@ class DirectRLEnv:
         """{source name: device tensor} of the rows the terms read; net: the contact report's dense net impulses
         are wanted, brought up to date (subclass hook)."""
         raise NotImplementedError(f"{type(self).__name__} does not serve cfg.rewards")
-
-    def _rewards_get_state(self) -> dict:
-        """The episodic sums, the step's term values, the last episode's sums and the previous actions (no keys
-        without cfg.rewards)."""
-        return {} if self._rewards is None else self._rewards.get_state()
-
-    def _rewards_set_state(self, state: dict) -> dict:
-        """Load the reward keys of a set_state dict; returns the dict without them."""
-        from .rewards import EnvRewards
-
-        if self._rewards is not None:
-            self._rewards.set_state(state)
-        return {k: v for k, v in state.items() if not EnvRewards.is_state_key(k)}
 
     # ------------------------------------------------------------------ action manager
     def _actions_start(self) -> None:
@@ -397,19 +392,6 @@ class DirectRLEnv:
     def _actions_attach(self, cmd: torch.Tensor) -> None:
         """Make the physics read its joint commands from ``cmd`` (N, joints) (subclass hook)."""
         raise NotImplementedError(f"{type(self).__name__} does not serve cfg.actions")
-
-    def _actions_get_state(self) -> dict:
-        """The manager's action, prev_action, processed, prev_applied and the command buffer (no keys without
-        cfg.actions)."""
-        return {} if self._action_terms is None else self._action_terms.get_state()
-
-    def _actions_set_state(self, state: dict) -> dict:
-        """Load the action keys of a set_state dict; returns the dict without them."""
-        from .actions import EnvActions
-
-        if self._action_terms is not None:
-            self._action_terms.set_state(state)
-        return {k: v for k, v in state.items() if not EnvActions.is_state_key(k)}
 
     # ------------------------------------------------------------------ termination manager
     def _terminations_start(self) -> None:
@@ -442,19 +424,6 @@ class DirectRLEnv:
         """Reset the envs of a device uint8 mask and write every env's observation row into ``obs``: one
         stream-ordered masked reset, no host read (subclass hook of cfg.terminations_reset)."""
         raise NotImplementedError(f"{type(self).__name__} does not serve cfg.terminations_reset")
-
-    def _terminations_get_state(self) -> dict:
-        """The term flags, time_outs / terminated / dones, the last episode's flags and the reset request (no keys
-        without cfg.terminations)."""
-        return {} if self._terminations is None else self._terminations.get_state()
-
-    def _terminations_set_state(self, state: dict) -> dict:
-        """Load the termination keys of a set_state dict; returns the dict without them."""
-        from .terminations import EnvTerminations
-
-        if self._terminations is not None:
-            self._terminations.set_state(state)
-        return {k: v for k, v in state.items() if not EnvTerminations.is_state_key(k)}
 
     @staticmethod
     def seed(seed: int = -1) -> int:
@@ -496,14 +465,10 @@ class DirectRLEnv:
         """Re-seed the device streams (subclasses extend it): here the Philox key of the noise models, of
         the interval events (whose timers stay as they are: DirectRLEnv never resets the event manager), of the
         command terms and of the observation terms' noise."""
-        if self._noise is not None:
-            self._noise.seed = int(seed)
-        if self._events is not None:
-            self._events.seed = int(seed)
-        if self._commands is not None:
-            self._commands.seed = int(seed)
-        if self._observations is not None:
-            self._observations.seed = int(seed)
+        for attr in _part_classes():
+            part = getattr(self, attr)
+            if hasattr(part, "seed"):  # (the rewards, terminations and actions draw nothing)
+                part.seed = int(seed)
 
     def _reset_impl(self):
         raise NotImplementedError

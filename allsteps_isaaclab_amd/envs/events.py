@@ -14,6 +14,7 @@ import torch
 
 from .. import _native
 from ..utils import events as E
+from ._manager import DeviceState, RowTerms, is_number
 
 
 def _unsupported(term: str, detail: str) -> "_native.NativeError":
@@ -21,16 +22,12 @@ def _unsupported(term: str, detail: str) -> "_native.NativeError":
                                f"fallback); supported: {E.SUPPORTED}")
 
 
-def _is_number(x) -> bool:
-    return isinstance(x, (int, float, np.floating, np.integer)) and not isinstance(x, bool)
-
-
 def _pair(x, term: str, what: str) -> tuple[float, float]:
     try:
         lo, hi = x
     except (TypeError, ValueError):
         raise _unsupported(term, f"{what} = {x!r} is not a (lo, hi) pair") from None
-    if not (_is_number(lo) and _is_number(hi)):
+    if not (is_number(lo) and is_number(hi)):
         raise _unsupported(term, f"{what} = {x!r} is not a pair of numbers")
     return float(lo), float(hi)
 
@@ -93,56 +90,18 @@ def term_row(name: str, cfg) -> np.ndarray:
     return row
 
 
-def parse_terms(events) -> list[tuple[str, object]]:
-    """(name, EventTermCfg) of cfg.events in cfg order: a dict, or an object whose attributes are the terms (the
-    reference's configclass; a plain class's class attributes count too).  None entries are skipped
-    (event_manager.py:337-338)."""
-    if isinstance(events, dict):
-        items = list(events.items())
-    else:
-        items = list(vars(events).items())
-        seen = {k for k, _ in items}
-        for klass in reversed(type(events).__mro__[:-1]):
-            items += [(k, v) for k, v in vars(klass).items()
-                      if k not in seen and not k.startswith("_") and isinstance(v, E.EventTermCfg)]
-            seen |= {k for k, _ in items}
-    out = []
-    for name, term in items:
-        if term is None or name.startswith("_"):
-            continue
-        if not isinstance(term, E.EventTermCfg):
-            raise TypeError(f"Configuration for the term '{name}' is not of type EventTermCfg. Received: "
-                            f"'{type(term)}'.")
-        out.append((name, term))
-    return out
+class EventTerms(RowTerms):
+    """The host side of cfg.events: names, cfgs and descriptor rows, checked (no device needed).  None entries are
+    skipped (event_manager.py:337-338)."""
+
+    NOUN, TERM_TYPE, WORDS = "event", E.EventTermCfg, _native.EVENT_TERM_FLOATS
+    LIMIT = ("AS_MAX_EVENT_TERMS", _native.MAX_EVENT_TERMS)
+
+    def row(self, name: str, cfg) -> np.ndarray:
+        return term_row(name, cfg)
 
 
-class EventTerms:
-    """The host side of cfg.events: names, cfgs and descriptor rows, checked (no device needed)."""
-
-    def __init__(self, events):
-        terms = parse_terms(events)
-        if len(terms) > _native.MAX_EVENT_TERMS:
-            raise _native.NativeError(f"cfg.events has {len(terms)} terms ({[k for k, _ in terms]}); the event "
-                                      f"kernel takes at most AS_MAX_EVENT_TERMS = {_native.MAX_EVENT_TERMS}")
-        self.names = [k for k, _ in terms]
-        self.cfgs = [c for _, c in terms]
-        self.rows = np.stack([term_row(k, c) for k, c in terms]) if terms else \
-            np.zeros((0, _native.EVENT_TERM_FLOATS), np.float32)
-
-    def index(self, term_name: str) -> int:
-        if term_name not in self.names:
-            raise ValueError(f"Event term '{term_name}' not found.")
-        return self.names.index(term_name)
-
-    def set(self, term_name: str, cfg) -> int:
-        k = self.index(term_name)
-        self.rows[k] = term_row(term_name, cfg)
-        self.cfgs[k] = cfg
-        return k
-
-
-class EnvEvents:
+class EnvEvents(DeviceState):
     """The events side of a DirectRLEnv: term descriptors, timers, stream counter and the fired mask."""
 
     STATE_KEYS = ("event_t", "event_time_left")
@@ -185,14 +144,10 @@ class EnvEvents:
     def tensors(self) -> dict:
         return {"event_t": self.t, "event_time_left": self.time_left}
 
-    def get_state(self) -> dict:
-        return {k: v.clone() for k, v in self.tensors().items()}
-
-    def set_state(self, state: dict) -> None:
-        for k, v in self.tensors().items():
-            if k in state:
-                v.copy_(torch.as_tensor(state[k]).to(v.device, v.dtype).reshape(v.shape))
-                self.started = True
+    def set_state(self, state: dict) -> bool:
+        loaded = super().set_state(state)
+        self.started = self.started or loaded  # (loaded timers are not drawn again)
+        return loaded
 
 
 class EventManagerView:

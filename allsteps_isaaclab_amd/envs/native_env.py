@@ -133,23 +133,28 @@ class NativeDirectEnv(DirectRLEnv):
                 "imu": None if im is None else im.data,
                 "ray_hits": None if hs is None else hs.hits, "ray_pose": None if hs is None else hs.pose}
 
+    def _foot_sensor_infos(self) -> dict:
+        """{name: SensorInfo} of the env's foot sensors, under their attribute names: what the reward and the
+        termination terms resolve a sensor_cfg against."""
+        from ._manager import SensorInfo
+
+        rep = self._report
+        return {name: SensorInfo(list(s.body_names), [0 if rep is None else rep.foot_body[f] for f in s._feet],
+                                 list(s._feet))
+                for name, s in vars(self).items() if isinstance(s, _FootSensor)}
+
     def _rewards_context(self):
-        from .rewards import RewContext, SensorInfo
+        from .rewards import RewContext
 
         d = self.robot.data
         rep, tm = self._report, self._contact_timers
-        sensors = {}
-        for name, s in vars(self).items():  # the env's foot sensors, under their attribute names
-            if isinstance(s, _FootSensor):
-                sensors[name] = SensorInfo(list(s.body_names),
-                                           [0 if rep is None else rep.foot_body[f] for f in s._feet], list(s._feet))
         return RewContext(
             joint_names=list(d.joint_names),
             default_joint_pos=d.default_joint_pos[0].detach().cpu().numpy(),
             soft_joint_pos_limits=d.soft_joint_pos_limits[0].detach().cpu().numpy(),
             action_cols=int(self.cfg.action_space), step_dt=self.step_dt,
             command_names=[] if self._commands is None else list(self._commands.terms.names),
-            sensors=sensors, contact_forces=rep is not None, contact_air_time=tm is not None)
+            sensors=self._foot_sensor_infos(), contact_forces=rep is not None, contact_air_time=tm is not None)
 
     def _rewards_sources(self, net: bool = False) -> dict:
         s, cm, rep, tm = self.state, self._commands, self._report, self._contact_timers
@@ -187,10 +192,7 @@ class NativeDirectEnv(DirectRLEnv):
 
         d = self.robot.data
         rep = self._report
-        sensors = {}
-        for name, s in vars(self).items():  # the env's foot sensors, under their attribute names
-            if isinstance(s, _FootSensor):
-                sensors[name] = SensorInfo(list(s.body_names), [0 if rep is None else rep.foot_body[f] for f in s._feet])
+        sensors = self._foot_sensor_infos()
         for name, s in self.scene.sensors.items():  # and the all-body contact sensor of cfg.contact_forces
             if isinstance(s, _ContactSensor):
                 sensors[name] = SensorInfo(list(s.body_names), list(range(s.num_bodies)))
@@ -248,9 +250,7 @@ class NativeDirectEnv(DirectRLEnv):
         (N,); uint8); with cfg.actions, the action manager's buffers (action_action, action_prev_action,
         action_processed, action_prev_applied, (N, columns); action_commands, (N, joints))."""
         tm, im = self._contact_timers, self._imus
-        return {**{k: v.clone() for k, v in self.state.items()}, **self._noise_get_state(),
-                **self._events_get_state(), **self._commands_get_state(), **self._observations_get_state(),
-                **self._rewards_get_state(), **self._terminations_get_state(), **self._actions_get_state(),
+        return {**{k: v.clone() for k, v in self.state.items()}, **self._parts_get_state(),
                 **({} if tm is None else tm.get_state()),
                 **({} if im is None else im.get_state())}
 
@@ -261,9 +261,7 @@ class NativeDirectEnv(DirectRLEnv):
         if self._imus is not None:  # (and every env is outdated)
             self._imus.set_state(state)
         state = {k: v for k, v in state.items() if k not in _ContactTimers.STATE_KEYS + _ImuSet.STATE_KEYS}
-        state = self._terminations_set_state(self._rewards_set_state(self._observations_set_state(state)))
-        state = self._actions_set_state(state)
-        for k, v in self._commands_set_state(self._events_set_state(self._noise_set_state(state))).items():
+        for k, v in self._parts_set_state(state).items():
             self.state[k].copy_(torch.as_tensor(v).to(self.state[k].device, self.state[k].dtype).reshape(
                 self.state[k].shape))
 

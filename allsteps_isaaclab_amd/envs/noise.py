@@ -14,6 +14,7 @@ import torch
 
 from .. import _native
 from ..utils import noise as N
+from ._manager import DeviceState, is_number
 
 _TERMS = {N.constant_noise: (_native.NOISE_CONSTANT, ("bias", None)),
           N.uniform_noise: (_native.NOISE_UNIFORM, ("n_min", "n_max")),
@@ -42,13 +43,9 @@ def _term(cfg, what: str):
     return kind, _native.NOISE_OPS[op], p0, p1
 
 
-def _is_number(x) -> bool:
-    return isinstance(x, (int, float, np.floating, np.integer)) and not isinstance(x, bool)
-
-
 def _vector(x, cols: int, device, what: str) -> torch.Tensor:
     """A parameter (float or tensor broadcastable to a row) as a float32 device vector [cols]."""
-    if _is_number(x):
+    if is_number(x):
         return torch.full((cols,), float(np.float32(x)), dtype=torch.float32, device=device)
     if not torch.is_tensor(x):
         raise _unsupported(what, f"parameter of type {type(x).__name__} (float or tensor expected)")
@@ -64,7 +61,7 @@ def _params(kind: int, p0, p1, cols: int, device, what: str):
     """The kernels' [cols] vectors.  Uniform: (n_min, w = n_max - n_min), w formed once as torch forms it --
     in double for two Python floats (rounded to float32 where it meets the data), in float32 with a tensor."""
     if kind == _native.NOISE_UNIFORM:
-        if _is_number(p0) and _is_number(p1):
+        if is_number(p0) and is_number(p1):
             w = float(p1) - float(p0)
         else:
             w = _vector(p1, cols, device, what) - _vector(p0, cols, device, what)
@@ -75,7 +72,7 @@ def _params(kind: int, p0, p1, cols: int, device, what: str):
 def _scalar(x, what: str) -> float:
     if torch.is_tensor(x) and x.numel() == 1:
         return float(x.detach().float().reshape(()).cpu())
-    if not _is_number(x):
+    if not is_number(x):
         raise ValueError(f"{what}: the bias term's parameters are one value per model (the bias is (num_envs, 1)), "
                          f"got {type(x).__name__}" + (f" of shape {tuple(x.shape)}" if torch.is_tensor(x) else ""))
     return float(x)
@@ -114,7 +111,7 @@ class NoiseModelState:
         self.desc = d
 
 
-class EnvNoise:
+class EnvNoise(DeviceState):
     """The noise side of a DirectRLEnv: both models, the stream counter and the noisy-action buffer."""
 
     STATE_KEYS = ("noise_t", "noise_action_bias", "noise_obs_bias")
@@ -168,11 +165,3 @@ class EnvNoise:
         if self.obs is not None and self.obs.bias is not None:
             d["noise_obs_bias"] = self.obs.bias
         return d
-
-    def get_state(self) -> dict:
-        return {k: v.clone() for k, v in self.tensors().items()}
-
-    def set_state(self, state: dict) -> None:
-        for k, v in self.tensors().items():
-            if k in state:
-                v.copy_(torch.as_tensor(state[k]).to(v.device, v.dtype).reshape(v.shape))

@@ -22,22 +22,18 @@ from ..utils import noise as NZ
 from ..utils import observations as OB
 from ..utils import sensors as SN
 from ..utils.observations import resolve_joint_ids  # noqa: F401  (re-exported)
+from ._manager import DeviceState, cfg_items, is_number, u8
 
 _SRC = {name: k for k, name in enumerate(_native.OBS_SOURCES)}
 _NOISE = {NZ.constant_noise: (_native.NOISE_CONSTANT, ("bias", None)),
           NZ.uniform_noise: (_native.NOISE_UNIFORM, ("n_min", "n_max")),
           NZ.gaussian_noise: (_native.NOISE_GAUSSIAN, ("mean", "std"))}
-STATE_PREFIX = "observation_"
 
 
 def _unsupported(group: str, term: str | None, detail: str) -> "_native.NativeError":
     where = f"cfg.observations group {group!r}" + ("" if term is None else f" term {term!r}")
     return _native.NativeError(f"{where}: {detail}.  The observations are assembled in a HIP kernel (no host "
                                f"fallback); supported: {OB.SUPPORTED}")
-
-
-def _is_number(x) -> bool:
-    return isinstance(x, (int, float, np.floating, np.integer)) and not isinstance(x, bool)
 
 
 @dataclass
@@ -168,7 +164,7 @@ def _term_source(func, params: dict, ctx: ObsContext, g: str, t: str):
             raise _unsupported(g, t, f"sensor_cfg names the sensor {sname!r}; the env's cfg has the ray casters "
                                      f"{sorted(ctx.ray_sensors)} (cfg.height_scanner)")
         offset = params.get("offset", 0.5)
-        if not _is_number(offset):
+        if not is_number(offset):
             raise _unsupported(g, t, f"offset = {offset!r} is not a number")
         R = int(ctx.ray_sensors[sname])
         return (_native.OBS_HEIGHT_SCAN, S["ray_hits"], [2 * R + r for r in range(R)], np.full(R, f32(offset), f32),
@@ -191,7 +187,7 @@ def _term_source(func, params: dict, ctx: ObsContext, g: str, t: str):
 
 def _per_column(x, width: int, g: str, t: str, what: str) -> np.ndarray:
     """A noise parameter -- a float, or per-column values (tuple, array or tensor) -- as float32 [width]."""
-    if _is_number(x):
+    if is_number(x):
         return np.full(width, np.float32(x), np.float32)
     try:
         v = np.asarray(x.detach().cpu().numpy() if torch.is_tensor(x) else x, dtype=np.float32).reshape(-1)
@@ -220,7 +216,7 @@ def _noise(cfg, width: int, g: str, t: str):
     x0 = getattr(cfg, n0)
     x1 = getattr(cfg, n1) if n1 else 0.0
     if kind == _native.NOISE_UNIFORM:  # w = n_max - n_min as torch forms it: in double for two floats
-        if _is_number(x0) and _is_number(x1):
+        if is_number(x0) and is_number(x1):
             w = np.full(width, f32(float(x1) - float(x0)), f32)
         else:
             w = _per_column(x1, width, g, t, "noise.n_max") - _per_column(x0, width, g, t, "noise.n_min")
@@ -277,35 +273,14 @@ def _get(cfg, key: str, default):
     return cfg.get(key, default) if isinstance(cfg, dict) else getattr(cfg, key, default)
 
 
-def _items(obj, is_entry) -> list:
-    """(name, value) of a cfg object in cfg order: a dict, or an object's attributes, then its classes' attributes
-    that pass ``is_entry`` (the reference's configclass turns those into instance fields)."""
-    if isinstance(obj, dict):
-        return list(obj.items())
-    items = list(vars(obj).items())
-    seen = {k for k, _ in items}
-    for klass in reversed(type(obj).__mro__[:-1]):
-        for k, v in vars(klass).items():
-            if k not in seen and not k.startswith("_") and is_entry(v):
-                items.append((k, v))
-                seen.add(k)
-    return items
-
-
 class GroupSpec:
     """One parsed group: its terms, the layout of its output and the device tables as host arrays."""
 
     def __init__(self, name: str, cfg, ctx: ObsContext):
         self.name, self.cfg = name, cfg
         self.concatenate = bool(_get(cfg, "concatenate_terms", True))
-        self.terms: list[TermSpec] = []
-        for tname, tcfg in _items(cfg, lambda v: isinstance(v, OB.ObservationTermCfg)):
-            if tname in OB.GROUP_SETTINGS or tcfg is None or tname.startswith("_"):
-                continue
-            if not isinstance(tcfg, OB.ObservationTermCfg):
-                raise TypeError(f"Configuration for the term '{tname}' is not of type ObservationTermCfg. Received: "
-                                f"'{type(tcfg)}'.")
-            self.terms.append(parse_term(name, tname, tcfg, cfg, ctx))
+        self.terms = [parse_term(name, tname, tcfg, cfg, ctx)
+                      for tname, tcfg in cfg_items(cfg, OB.ObservationTermCfg, ignore=OB.GROUP_SETTINGS)]
         if not self.terms:
             raise _unsupported(name, None, "the group has no terms")
         if len(self.terms) > _native.MAX_OBS_TERMS:
@@ -366,18 +341,17 @@ class GroupSpec:
         return used
 
 
+def _not_a_group(name: str, cfg) -> TypeError:
+    return TypeError(f"Observation group '{name}' is not of type 'ObservationGroupCfg'. Received: '{type(cfg)}'.")
+
+
 class ObservationGroups:
     """The host side of cfg.observations: groups in cfg order, checked (no device needed)."""
 
     def __init__(self, observations, ctx: ObsContext):
         self.ctx = ctx
         self.groups: list[GroupSpec] = []
-        for gname, gcfg in _items(observations, lambda v: isinstance(v, (OB.ObservationGroupCfg, dict))):
-            if gcfg is None or gname.startswith("_"):
-                continue
-            if not isinstance(gcfg, (OB.ObservationGroupCfg, dict)):
-                raise TypeError(f"Observation group '{gname}' is not of type 'ObservationGroupCfg'. Received: "
-                                f"'{type(gcfg)}'.")
+        for gname, gcfg in cfg_items(observations, (OB.ObservationGroupCfg, dict), error=_not_a_group):
             if gname == "policy":
                 raise _unsupported(gname, None, "'policy' is the task's own observation, which stays as it is: give "
                                                 "the group another name")
@@ -432,9 +406,11 @@ class ObservationGroups:
         return msg
 
 
-class EnvObservations:
+class EnvObservations(DeviceState):
     """The observations side of a DirectRLEnv: per group the device tables, the output rows (which hold the
     history), the push counts and the stream counter."""
+
+    STATE_PREFIX = "observation_"
 
     def __init__(self, cfg, env, n: int, device, seed: int):
         self.n, self.device, self.seed = n, device, int(seed)
@@ -463,10 +439,6 @@ class EnvObservations:
     @staticmethod
     def wanted(cfg) -> bool:
         return getattr(cfg, "observations", None) is not None
-
-    @staticmethod
-    def is_state_key(k: str) -> bool:
-        return k.startswith(STATE_PREFIX)
 
     # ---- launches
     def _refresh_sensors(self) -> None:
@@ -509,8 +481,7 @@ class EnvObservations:
     def reset(self, mask) -> None:
         """ObservationManager.reset(env_ids) for the envs of a uint8 / bool mask (None: all): no compute."""
         if mask is not None:
-            mask = mask.to(self.device).reshape(self.n)
-            mask = mask.view(torch.uint8) if mask.dtype == torch.bool else mask.to(torch.uint8)
+            mask = u8(mask.to(self.device).reshape(self.n))
         for k in range(len(self.spec.groups)):
             _native.observations_reset(self.out[k], self.count[k], mask=mask, stream=self._env._noise_stream())
             self.launches += 1
@@ -525,17 +496,9 @@ class EnvObservations:
 
     # ---- state (get_state / set_state of the envs)
     def tensors(self) -> dict:
-        d = {STATE_PREFIX + "t": self.t, STATE_PREFIX + "count": self.count}
-        d.update({f"{STATE_PREFIX}history_{g.name}": self.out[k] for k, g in enumerate(self.spec.groups)})
+        d = {"observation_t": self.t, "observation_count": self.count}
+        d.update({f"observation_history_{g.name}": self.out[k] for k, g in enumerate(self.spec.groups)})
         return d
-
-    def get_state(self) -> dict:
-        return {k: v.clone() for k, v in self.tensors().items()}
-
-    def set_state(self, state: dict) -> None:
-        for k, v in self.tensors().items():
-            if k in state:
-                v.copy_(torch.as_tensor(state[k]).to(v.device, v.dtype).reshape(v.shape))
 
 
 class ObservationManagerView:

@@ -13,37 +13,25 @@ takes effect in a graph that is already captured.
 from __future__ import annotations
 
 from dataclasses import dataclass, field
+from functools import partial
 
 import numpy as np
 import torch
 
 from .. import _native
 from ..utils import terminations as TM
-from ..utils.observations import resolve_joint_ids
-from ..utils.rewards import resolve_body_ids
+from . import _manager as M
+from ._manager import SensorInfo, u8  # noqa: F401  (SensorInfo: re-exported)
 
 _KIND = {name: k for k, name in enumerate(_native.TERMINATION_KINDS)}
 _FUNCS = {getattr(TM, name): name for name in TM.SERVED}
 _REFUSED = {getattr(TM, name): name for name in TM.REFUSED}
-STATE_PREFIX = "termination_"
 
 
 def _unsupported(term: str | None, detail: str) -> "_native.NativeError":
     where = "cfg.terminations" + ("" if term is None else f" term {term!r}")
     return _native.NativeError(f"{where}: {detail}.  The terminations are computed in a HIP kernel (no host fallback); "
                                f"supported: {TM.SUPPORTED}")
-
-
-def _is_number(x) -> bool:
-    return isinstance(x, (int, float, np.floating, np.integer)) and not isinstance(x, bool)
-
-
-@dataclass
-class SensorInfo:
-    """A contact sensor as the terms address it: its bodies' names, and per body the row of the net forces."""
-
-    body_names: list
-    net_bodies: list  # body b of the sensor -> body row of the contact report's net impulses
 
 
 @dataclass
@@ -76,64 +64,14 @@ class TermSpec:
     i0: int = 0
 
 
-def _params(params: dict, required: tuple, optional: tuple, t: str) -> None:
-    extra = sorted(set(params) - set(required) - set(optional))
-    if extra:
-        raise _unsupported(t, f"params {extra} are not parameters of the term function (it takes "
-                              f"{list(required + optional)})")
-    missing = [k for k in required if k not in params]
-    if missing:
-        raise _unsupported(t, f"the term function needs params {missing}")
-
-
-def _number(x, key: str, t: str) -> np.float32:
-    """A Python scalar as torch takes it in an operation with a float32 tensor."""
-    if not _is_number(x):
-        raise _unsupported(t, f"{key} = {x!r} is not a number")
-    return np.float32(x)
-
-
-def _robot_asset(params: dict, t: str):
-    asset = params.get("asset_cfg", None)
-    if asset is None:
-        return TM.SceneEntityCfg("robot")
-    if not hasattr(asset, "name"):
-        raise _unsupported(t, f"params['asset_cfg'] = {asset!r} is not a SceneEntityCfg")
-    if asset.name != "robot":
-        raise _unsupported(t, f"asset_cfg.name = {asset.name!r} is not 'robot' (the env's articulation)")
-    return asset
+_params = partial(M.check_params, _unsupported)
+_number = partial(M.number, _unsupported)
+_robot_asset = partial(M.robot_asset, _unsupported)
+_sensor_bodies = partial(M.sensor_bodies, _unsupported)
 
 
 def _joints(params: dict, ctx: TermContext, t: str) -> list:
-    asset = _robot_asset(params, t)
-    try:
-        ids = resolve_joint_ids(asset, ctx.joint_names, "asset_cfg")
-    except ValueError as e:
-        raise _unsupported(t, str(e)) from None
-    ids = list(range(len(ctx.joint_names))) if ids is None else ids
-    if not ids:
-        raise _unsupported(t, "asset_cfg selects no joint")
-    return ids
-
-
-def _sensor_bodies(params: dict, ctx: TermContext, t: str) -> list:
-    """The rows of the net forces that sensor_cfg's bodies read."""
-    if not ctx.contact_forces:
-        raise _unsupported(t, "the term reads the contact sensors' net forces: set cfg.contact_forces")
-    sensor = params.get("sensor_cfg", None)
-    sname = getattr(sensor, "name", None)
-    if sname not in ctx.sensors:
-        raise _unsupported(t, f"sensor_cfg names the sensor {sname!r}; the env has the contact sensors "
-                              f"{sorted(ctx.sensors)}")
-    info = ctx.sensors[sname]
-    try:
-        ids = resolve_body_ids(sensor, info.body_names, "sensor_cfg")
-    except ValueError as e:
-        raise _unsupported(t, str(e)) from None
-    ids = list(range(len(info.body_names))) if ids is None else ids
-    if not ids:
-        raise _unsupported(t, "sensor_cfg selects no body")
-    return [int(info.net_bodies[k]) for k in ids]
+    return M.joint_ids(_unsupported, _robot_asset(params, t), ctx.joint_names, t)
 
 
 def parse_term(t: str, cfg, ctx: TermContext) -> TermSpec:
@@ -210,83 +148,28 @@ def parse_term(t: str, cfg, ctx: TermContext) -> TermSpec:
     return spec
 
 
-def _items(obj) -> list:
-    """(name, value) of a cfg object in cfg order: a dict, or an object's attributes, then its classes' attributes
-    that are TerminationTermCfg (the reference's configclass turns those into instance fields)."""
-    if isinstance(obj, dict):
-        return list(obj.items())
-    items = [(k, v) for k, v in vars(obj).items() if not k.startswith("_")]
-    seen = {k for k, _ in items}
-    for klass in reversed(type(obj).__mro__[:-1]):
-        for k, v in vars(klass).items():
-            if k not in seen and not k.startswith("_") and isinstance(v, TM.TerminationTermCfg):
-                items.append((k, v))
-                seen.add(k)
-    return items
-
-
-class TerminationTerms:
+class TerminationTerms(M.TermTable):
     """The host side of cfg.terminations: the terms in cfg order, checked (no device needed), and the device tables
     as host arrays."""
 
-    def __init__(self, terminations, ctx: TermContext):
-        self.ctx = ctx
-        self.terms: list[TermSpec] = []
-        for name, cfg in _items(terminations):
-            if cfg is None:  # (as the reference's _prepare_terms)
-                continue
-            self.terms.append(parse_term(name, cfg, ctx))
-        if not self.terms:
-            raise _unsupported(None, "there are no terms")
-        if len(self.terms) > _native.MAX_TERMINATION_TERMS:
-            raise _unsupported(None, f"{len(self.terms)} terms; the termination kernel takes at most "
-                                     f"AS_MAX_TERMINATION_TERMS = {_native.MAX_TERMINATION_TERMS}")
-        self.build()
+    NOUN, TERM_TYPE, KINDS = "Termination", TM.TerminationTermCfg, _native.TERMINATION_KINDS
+    WORDS = _native.TERMINATION_TERM_WORDS
+    TABLE = (_native.TERMINATION_TABLE_ROWS, _native.MAX_TERMINATION_TERMS, _native.MAX_TERMINATION_IDS)
+    LIMIT, COLUMN, MAY_CHANGE = "AS_MAX_TERMINATION_TERMS", ("Time Out", str.center), "params and time_out"
+    parse_term, unsupported = staticmethod(parse_term), staticmethod(_unsupported)
 
-    names = property(lambda self: [t.name for t in self.terms])
+    def pack(self, row, ints, t: TermSpec) -> None:
+        ints[0], ints[1], ints[2], ints[3] = t.kind, int(t.time_out), len(t.ids), t.row
+        row[4], row[5], ints[6] = t.p0, t.p1, t.i0
 
-    def build(self) -> None:
-        """The descriptor rows, the index table and the kinds mask from the term specs as they stand."""
-        f32, i32 = np.float32, np.int32
-        rows = np.zeros((len(self.terms), _native.TERMINATION_TERM_WORDS), f32)
-        table = np.zeros((_native.TERMINATION_TABLE_ROWS, _native.MAX_TERMINATION_TERMS, _native.MAX_TERMINATION_IDS),
-                         f32)
-        for k, t in enumerate(self.terms):
-            ints = rows[k].view(i32)
-            ints[0], ints[1], ints[2], ints[3] = t.kind, int(t.time_out), len(t.ids), t.row
-            rows[k, 4], rows[k, 5], ints[6] = t.p0, t.p1, t.i0
-            table[0, k, :len(t.ids)] = np.asarray(t.ids, i32).view(f32)
-            table[1, k, :len(t.a)] = t.a
-            table[2, k, :len(t.b)] = t.b
-        self.rows, self.table = rows, table
-        self.kinds = 0
-        for t in self.terms:
-            self.kinds |= 1 << t.kind
-
-    def index(self, term_name: str) -> int:
-        if term_name not in self.names:
-            raise ValueError(f"Termination term '{term_name}' not found.")
-        return self.names.index(term_name)
-
-    def uses(self, *kinds: str) -> bool:
-        return any(_native.TERMINATION_KINDS[t.kind] in kinds for t in self.terms)
-
-    def table_str(self) -> str:
-        """TerminationManager.__str__ in the reference's form."""
-        rows = [(str(i), t.name, str(bool(t.cfg.time_out))) for i, t in enumerate(self.terms)]
-        head = ("Index", "Name", "Time Out")
-        w = [max(len(r[j]) for r in rows + [head]) for j in range(3)]
-        line = "+" + "+".join("-" * (x + 2) for x in w) + "+\n"
-        total = len(line) - 3
-        fmt = lambda r: "| " + " | ".join((r[0].center(w[0]), r[1].ljust(w[1]), r[2].center(w[2]))) + " |\n"  # noqa: E731
-        msg = f"<TerminationManager> contains {len(rows)} active terms.\n"
-        msg += "+" + "-" * total + "+\n" + "|" + "Active Termination Terms".center(total) + "|\n"
-        msg += line + "| " + " | ".join(h.center(x) for h, x in zip(head, w)) + " |\n" + line
-        return msg + "".join(fmt(r) for r in rows) + line
+    def column(self, t: TermSpec) -> str:
+        return str(bool(t.cfg.time_out))
 
 
-class EnvTerminations:
+class EnvTerminations(M.DeviceState):
     """The terminations side of a DirectRLEnv: the device tables and the manager's buffers."""
+
+    STATE_PREFIX = "termination_"
 
     def __init__(self, cfg, env, n: int, device):
         self.n, self.device = n, device
@@ -311,17 +194,13 @@ class EnvTerminations:
     def wanted(cfg) -> bool:
         return getattr(cfg, "terminations", None) is not None
 
-    @staticmethod
-    def is_state_key(k: str) -> bool:
-        return k.startswith(STATE_PREFIX)
-
     # ---- launches
     def compute(self, terminated=None, truncated=None) -> torch.Tensor:
         """One launch: every term on the env's state as it stands.  terminated / truncated: the step's own flags
         ((n,) bool / uint8; None: no env was reset by the step).  Returns dones (n,) uint8."""
         env, spec = self._env, self.spec
         tensors = env._terminations_sources(net=spec.uses("illegal_contact"))
-        tensors["step_terminated"], tensors["step_truncated"] = _u8(terminated), _u8(truncated)
+        tensors["step_terminated"], tensors["step_truncated"] = u8(terminated), u8(truncated)
         src = _native.make_termination_sources(tensors, env.physics_dt)
         _native.terminations_step(self.desc, self.table, spec.kinds, src, self.term_dones, self.time_outs,
                                   self.terminated, self.dones, self.last_episode_dones, self.reset_request,
@@ -345,38 +224,14 @@ class EnvTerminations:
         return (obs, out[1], self.step_terminated, self.step_truncated, *out[4:])
 
     def set_term_cfg(self, term_name: str, cfg) -> None:
-        k = self.spec.index(term_name)
-        new, old = parse_term(term_name, cfg, self.spec.ctx), self.spec.terms[k]
-        if new.kind != old.kind:  # (the sources a launch is given, a captured one too, follow the kinds)
-            kinds = _native.TERMINATION_KINDS
-            raise _unsupported(term_name, f"the new cfg changes the term's function from {kinds[old.kind]} to "
-                                          f"{kinds[new.kind]}; the terms' functions are fixed at construction (params "
-                                          f"and time_out may change)")
-        self.spec.terms[k] = new
-        self.spec.build()
-        self.desc.copy_(torch.as_tensor(self.spec.rows.copy()))
-        self.table.copy_(torch.as_tensor(self.spec.table.copy()))
+        self.spec.replace(term_name, cfg, self.desc, self.table)
 
     # ---- state (get_state / set_state of the envs)
     def tensors(self) -> dict:
-        return {STATE_PREFIX + "term_dones": self.term_dones, STATE_PREFIX + "time_outs": self.time_outs,
-                STATE_PREFIX + "terminated": self.terminated, STATE_PREFIX + "dones": self.dones,
-                STATE_PREFIX + "last_episode_dones": self.last_episode_dones,
-                STATE_PREFIX + "reset_request": self.reset_request}
-
-    def get_state(self) -> dict:
-        return {k: v.clone() for k, v in self.tensors().items()}
-
-    def set_state(self, state: dict) -> None:
-        for k, v in self.tensors().items():
-            if k in state:
-                v.copy_(torch.as_tensor(state[k]).to(v.device, v.dtype).reshape(v.shape))
-
-
-def _u8(x):
-    if x is None:
-        return None
-    return x.view(torch.uint8) if x.dtype == torch.bool else x.to(torch.uint8)
+        return {"termination_term_dones": self.term_dones, "termination_time_outs": self.time_outs,
+                "termination_terminated": self.terminated, "termination_dones": self.dones,
+                "termination_last_episode_dones": self.last_episode_dones,
+                "termination_reset_request": self.reset_request}
 
 
 class TerminationManagerView:
