@@ -47,18 +47,47 @@
 
 namespace as {
 
-template <int NV, uint64_t SKIP>
-__global__ __launch_bounds__(kStepThreads) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_step(StepArgs P) {
-  __shared__ Smem sm;
+typedef const __attribute__((address_space(4))) StepArgs KArgs;  // the launch arguments in the kernarg segment
+
+// The workgroup's LDS: the stamps' accumulators exist in the diagnostic twin alone.
+template <bool kDiag>
+struct StepLds {
+  Smem sm;
+};
+template <>
+struct StepLds<true> {
+  Smem sm;
+  unsigned long long stamp_acc[kNumStamps];
+};
+
+// The body of k_step (kDiag = false) and of its diagnostic twin k_step_diag (kDiag = true): the same code, with
+// Stamp<kDiag> for the phase stamps.  kargs: where the calling kernel's StepArgs parameter lies in its kernarg
+// segment (step_kargs below), handed in by the kernel, which alone knows its parameter list.
+template <int NV, uint64_t SKIP, bool kDiag>
+__device__ __forceinline__ void step_body(const StepArgs& P, KArgs* kargs) {
+  __shared__ StepLds<kDiag> lds;
+  Smem& sm = lds.sm;
   // model / plan constants stay in global memory (5.7 KB, L1/K$-resident): LDS is the occupancy
   // budget, see EnvS
-  CK* Kc = (CK*)P.consts;
+  // The launch arguments that live across the substep loop (the constants pointer, n, the report pointer below)
+  // are read through an opaque copy of the pointer to the arguments in the kernarg segment, a scalar load and
+  // a register of its own each.  As parts of the wide scalar loads that fetch
+  // the other arguments, a spill across the loop saved and restored the whole 4- or 16-register load for the
+  // one pointer, inside the loop.
+  KArgs* ka = kargs;
+  asm volatile("" : "+s"(ka));
+  CK* Kc = (CK*)ka->consts;
   const Consts& K = *(const Consts*)Kc;
   const int el = threadIdx.x >> 5, lane = threadIdx.x & 31;
-  const int n = P.n;
+  const int n = ka->n;
   EnvS& s = sm.env[el];
   const as_state_t& st = P.st;
-  Stamp ts{P.stamps, sm.stamp_acc, 0ull};
+  Stamp<kDiag> ts;
+  if constexpr (kDiag) {
+    ts.p = P.stamps;
+    ts.acc = lds.stamp_acc;
+    ts.t = 0ull;
+  }
   ts.start();
   // ---- load, batch 1: everything whose address is known at launch start, issued together -- the env
   //      of this half, this lane's table row (allsteps_lane_table.h), the curriculum level and both
@@ -173,20 +202,28 @@ __global__ __launch_bounds__(kStepThreads) __attribute__((amdgpu_waves_per_eu(2,
   // ---- physics
   if (do_physics) {
     const int substeps = Kc->sim.substeps;  // (through the generic reference it was re-read every substep)
+    const ReportDesc* rep = ka->rep;
     // (counted down: `left` substeps follow this one, which is also its slot in the contact report)
     for (int left = substeps - 1; left >= 0; --left) {
       // the opt-in contact report (step_report.h): a wave-uniform test of a launch argument per substep
       // (each test on an opaque copy of the pointer: no predicate of it is formed ahead of the loop and
       // held, spilled, across the substeps)
-      const ReportDesc* rp = P.rep;
+      const ReportDesc* rp = rep;
       asm volatile("" : "+s"(rp));
       if (rp && left == 0) report_store_qd(rp, n, Kc, s, lane, e, valid);
       substep<NV, SKIP>(K, sm, s, lane, tp, gc, lc, mask, ts);
-      rp = P.rep;
+      rp = rep;
       asm volatile("" : "+s"(rp));
       if (rp) report_store(rp, n, s, lane, e, valid, left);
     }
   }
+  // The launch arguments again, through a second opaque copy of that pointer: everything after the
+  // substeps reads its pointers and words of the launch by scalar loads here, instead of holding them in SGPRs
+  // -- spilled, there are some 70 of them -- across the substep loop.
+  KArgs* qa = kargs;
+  asm volatile("" : "+s"(qa));
+  KArgs& Q = *qa;
+  const __attribute__((address_space(4))) as_state_t& sq = Q.st;
   // This lane's reset constants (joint `lane` in cfg order: its link and limits, the start pose plain and
   // mirrored), loaded ahead of the final FK so that their global loads (L2 round trips) run under it
   // instead of heading the reset (the memory clobber keeps them there, not sunk into the reset
@@ -202,9 +239,9 @@ __global__ __launch_bounds__(kStepThreads) __attribute__((amdgpu_waves_per_eu(2,
   const float rs_lo = __uint_as_float(rr9.y), rs_hi = __uint_as_float(rr9.z);
   const int rs_li = (int)rr9.w;
   float rd_m = 0.f, rd_n = 0.f;  // mirror draw, this lane's joint-noise draw
-  if (P.reset_draws && P.mode != kModePhysics) {
-    rd_m = P.reset_draws[(size_t)e * 22];
-    rd_n = P.reset_draws[(size_t)e * 22 + 1 + lh];
+  if (Q.reset_draws && Q.mode != kModePhysics) {
+    rd_m = Q.reset_draws[(size_t)e * 22];
+    rd_n = Q.reset_draws[(size_t)e * 22 + 1 + lh];
   }
   asm volatile("" ::: "memory");
   if (do_physics) {
@@ -230,7 +267,7 @@ __global__ __launch_bounds__(kStepThreads) __attribute__((amdgpu_waves_per_eu(2,
   uint32_t episode = s.pk[kPkEpisode];
   bool done = false;
   Useful u{};  // tick #1's; its h / roll / pitch serve tick #2 where the pose cannot have changed (below)
-  if (P.mode == kModeStep || P.mode == kModeTask) {
+  if (Q.mode == kModeStep || Q.mode == kModeTask) {
     ep_len += 1;                                         // direct_rl_env.py:351
     compute_useful(T, s.root_pos, s.root_quat, bp, s.stones, 1, s.mask[0], s.mask[1], idx, prev, next, count,
                    swing, pot, old_pot, fc, true, u);    // allsteps_env.py:397 tick #1
@@ -280,14 +317,14 @@ __global__ __launch_bounds__(kStepThreads) __attribute__((amdgpu_waves_per_eu(2,
     float rew = terminated ? T.death : total;
     done = terminated || time_out;
     if (valid && lane == 0) {
-      P.reward[e] = rew;
-      P.terminated[e] = terminated ? 1 : 0;
-      P.truncated[e] = time_out ? 1 : 0;
+      Q.reward[e] = rew;
+      Q.terminated[e] = terminated ? 1 : 0;
+      Q.truncated[e] = time_out ? 1 : 0;
     }
-  } else if (P.mode == kModeReset) {
-    done = P.reset_mask == nullptr || P.reset_mask[e] != 0;
+  } else if (Q.mode == kModeReset) {
+    done = Q.reset_mask == nullptr || Q.reset_mask[e] != 0;
   }
-  if (P.mode != kModePhysics) {
+  if (Q.mode != kModePhysics) {
     // curriculum mean over the tick-#1 indices and the any-reset flag: one atomic per wave into a
     // striped partial sum, the flag by plain store
     const int cidx = valid ? idx : 0;
@@ -298,10 +335,10 @@ __global__ __launch_bounds__(kStepThreads) __attribute__((amdgpu_waves_per_eu(2,
     const int ndr = valid ? s.ndrop : 0;
     const int wdrop = __builtin_amdgcn_readlane(ndr, 0) + __builtin_amdgcn_readlane(ndr, 32);
     if (threadIdx.x == 0) {
-      atomicAdd(&P.counters[kCntStride * (1 + (int)(blockIdx.x % kCntSlots))], wsum);
-      if (wdrop) atomicAdd(&P.counters[kCntDropped], wdrop);
-      if (wdone) P.counters[0] = 1;
-      if (T.regen_footsteps) P.counters[kCntLevel] = cur;  // same value from every wave
+      atomicAdd(&Q.counters[kCntStride * (1 + (int)(blockIdx.x % kCntSlots))], wsum);
+      if (wdrop) atomicAdd(&Q.counters[kCntDropped], wdrop);
+      if (wdone) Q.counters[0] = 1;
+      if (T.regen_footsteps) Q.counters[kCntLevel] = cur;  // same value from every wave
     }
   }
   ts.mark(kStTask);
@@ -309,17 +346,17 @@ __global__ __launch_bounds__(kStepThreads) __attribute__((amdgpu_waves_per_eu(2,
   const bool any_done = __any(done);  // wave-uniform: both envs of the wave enter the FK together
   // regen_footsteps: the over-half test on the PRE-reset target index (allsteps_env.py:497-500 as
   // intended); k_obs draws the new course once the launch-wide curriculum gate is known
-  const bool regen = T.regen_footsteps && P.mode != kModePhysics && done && idx > T.num_steps / 2;
-  if (P.mode != kModePhysics && any_done) {
+  const bool regen = T.regen_footsteps && Q.mode != kModePhysics && done && idx > T.num_steps / 2;
+  if (Q.mode != kModePhysics && any_done) {
     if (done) {
       float dm = rd_m, dn = rd_n;  // the caller's draws (loaded ahead of the final FK), or Philox
-      if (!P.reset_draws) {
+      if (!Q.reset_draws) {
         float blk[4];
-        philox_block(P.seed, (uint32_t)(P.env_offset + e), episode, 0u, kResetTag, blk);
+        philox_block(Q.seed, (uint32_t)(Q.env_offset + e), episode, 0u, kResetTag, blk);
         dm = blk[0];
         if (lane < nh) {  // draw k = 1 + lane lives in block (1 + lane) / 4, slot (1 + lane) % 4
           const int k = 1 + lane;
-          philox_block(P.seed, (uint32_t)(P.env_offset + e), episode, (uint32_t)(k >> 2), kResetTag, blk);
+          philox_block(Q.seed, (uint32_t)(Q.env_offset + e), episode, (uint32_t)(k >> 2), kResetTag, blk);
           const int sl = k & 3;
           dn = sl == 0 ? blk[0] : (sl == 1 ? blk[1] : (sl == 2 ? blk[2] : blk[3]));
         }
@@ -369,7 +406,7 @@ __global__ __launch_bounds__(kStepThreads) __attribute__((amdgpu_waves_per_eu(2,
   //      condition.  The tick is applied here as if some env reset (true at any realistic env
   //      count); the tick-#1 state and the tick-dependent observation entries (foot contact,
   //      targets) go to a side buffer, and k_obs restores them in a launch where no env reset.
-  if (P.obs) {
+  if (Q.obs) {
     int i2 = idx, p2 = prev, n2 = next, c2 = count, w2 = swing;
     float pot2 = pot, op2 = old_pot, fc2[2] = {fc[0], fc[1]};
     // h, roll and pitch depend on root_quat and bp alone, which only a reset changes between the ticks:
@@ -377,9 +414,9 @@ __global__ __launch_bounds__(kStepThreads) __attribute__((amdgpu_waves_per_eu(2,
     // asin / two rem2pi
     Useful u2 = u;
     compute_useful(T, s.root_pos, s.root_quat, bp, s.stones, 1, s.mask[0], s.mask[1], i2, p2, n2, c2, w2, pot2,
-                   op2, fc2, true, u2, any_done || !(P.mode == kModeStep || P.mode == kModeTask));
+                   op2, fc2, true, u2, any_done || !(Q.mode == kModeStep || Q.mode == kModeTask));
     float* ob = s.x.obs;
-    uint32_t* side = P.side;
+    uint32_t* side = Q.side;
     if (lane == 0) {
       ob[0] = u2.h;
       ob[1] = u2.roll;
@@ -409,7 +446,7 @@ __global__ __launch_bounds__(kStepThreads) __attribute__((amdgpu_waves_per_eu(2,
     }
     __syncthreads();
     if (valid) {
-      float* orow = P.obs + (size_t)e * AS_OBS_DIM;
+      float* orow = Q.obs + (size_t)e * AS_OBS_DIM;
       orow[lane] = ob[lane];
       if (lane < AS_OBS_DIM - 32) orow[32 + lane] = ob[32 + lane];
       if (lane == 0) {
@@ -428,42 +465,57 @@ __global__ __launch_bounds__(kStepThreads) __attribute__((amdgpu_waves_per_eu(2,
   // ---- store
   if (valid) {
     if (lane < 3) {
-      st.root_pos[lane * n + e] = s.root_pos[lane];
-      st.root_lin[lane * n + e] = s.u[lane];
-      st.root_ang[lane * n + e] = s.u[3 + lane];
+      sq.root_pos[lane * n + e] = s.root_pos[lane];
+      sq.root_lin[lane * n + e] = s.u[lane];
+      sq.root_ang[lane * n + e] = s.u[3 + lane];
     }
-    if (lane < 4) st.root_quat[lane * n + e] = s.root_quat[lane];
+    if (lane < 4) sq.root_quat[lane * n + e] = s.root_quat[lane];
     if (lane < nh) {
       int i = rs_li - 1;
-      st.q[lane * n + e] = s.qi[i];
-      st.qd[lane * n + e] = s.u[6 + i];
+      sq.q[lane * n + e] = s.qi[i];
+      sq.qd[lane * n + e] = s.u[6 + i];
     }
     if (lane < 9) {
       float v = bp[0];
 #pragma unroll
       for (int k = 1; k < 9; ++k) v = (lane == k) ? bp[k] : v;
-      st.body_pos[lane * n + e] = v;
+      sq.body_pos[lane * n + e] = v;
     }
     if (lane == 0) {
       // an env reset in this launch starts the next one from the spawn pose in the air: no rows
       // (its fallen-state rows predicted a heavy wave that was not; C3 +1 %, r06q)
-      P.side[kSideCost * n + e] = done ? 0u : (uint32_t)s.nrows;
-      st.contact_mask[e] = s.mask[0];
-      st.contact_mask[n + e] = s.mask[1];
-      if (st.contact_mask_hind) {
-        st.contact_mask_hind[e] = s.mask[2];
-        st.contact_mask_hind[n + e] = s.mask[3];
+      Q.side[kSideCost * n + e] = done ? 0u : (uint32_t)s.nrows;
+      sq.contact_mask[e] = s.mask[0];
+      sq.contact_mask[n + e] = s.mask[1];
+      if (sq.contact_mask_hind) {
+        sq.contact_mask_hind[e] = s.mask[2];
+        sq.contact_mask_hind[n + e] = s.mask[3];
       }
-      if (P.mode != kModePhysics) {
-        st.idx[e] = idx; st.prev[e] = prev; st.next[e] = next; st.count[e] = count; st.swing[e] = swing;
-        st.ep_len[e] = ep_len; st.pot[e] = pot; st.old_pot[e] = old_pot;
-        st.foot_contact[e] = fc[0]; st.foot_contact[n + e] = fc[1];
-        st.episode[e] = episode;
+      if (Q.mode != kModePhysics) {
+        sq.idx[e] = idx; sq.prev[e] = prev; sq.next[e] = next; sq.count[e] = count; sq.swing[e] = swing;
+        sq.ep_len[e] = ep_len; sq.pot[e] = pot; sq.old_pot[e] = old_pot;
+        sq.foot_contact[e] = fc[0]; sq.foot_contact[n + e] = fc[1];
+        sq.episode[e] = episode;
       }
     }
   }
   ts.mark(kStStore);
   ts.flush();
+}
+
+// The StepArgs of a kernel whose one parameter it is, by value: the explicit arguments start the kernarg segment,
+// so it lies at offset 0.  Only such a kernel may call this (k_step and k_step_diag below do, for step_body).
+__device__ __forceinline__ KArgs* step_kargs() { return (KArgs*)__builtin_amdgcn_kernarg_segment_ptr(); }
+
+template <int NV, uint64_t SKIP>
+__global__ __launch_bounds__(kStepThreads) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_step(StepArgs P) {
+  step_body<NV, SKIP, false>(P, step_kargs());
+}
+
+// the twin with the diagnostic stamps (as_debug_stamps): launched exactly when StepArgs::stamps is set
+template <int NV, uint64_t SKIP>
+__global__ __launch_bounds__(kStepThreads) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_step_diag(StepArgs P) {
+  step_body<NV, SKIP, true>(P, step_kargs());
 }
 
 }  // namespace as
@@ -493,16 +545,25 @@ namespace as {
 // (model/anymal_c.xml, 6 + 12 hinges), stepped through as_physics_step.
 bool step_supported_nv(int nv) { return nv == 27 || nv == 18; }
 
+template <int NV, uint64_t SKIP>
+static void launch_step_twin(const StepArgs& a, hipStream_t stream) {
+  const int blocks = (a.n + EPB - 1) / EPB;
+  if (a.stamps)
+    hipLaunchKernelGGL((k_step_diag<NV, SKIP>), dim3(blocks), dim3(kStepThreads), 0, stream, a);
+  else
+    hipLaunchKernelGGL((k_step<NV, SKIP>), dim3(blocks), dim3(kStepThreads), 0, stream, a);
+}
+
+// the diagnostic twin exactly when the stamps are on (a.stamps != nullptr), the production kernel otherwise
 hipError_t launch_step(const StepArgs& a, int nv, bool sweep_skip, hipStream_t stream) {
-  int blocks = (a.n + EPB - 1) / EPB;
   if (nv == 27 && sweep_skip)
-    hipLaunchKernelGGL((k_step<27, kSweepSkip27>), dim3(blocks), dim3(kStepThreads), 0, stream, a);
+    launch_step_twin<27, kSweepSkip27>(a, stream);
   else if (nv == 27)
-    hipLaunchKernelGGL((k_step<27, 0ull>), dim3(blocks), dim3(kStepThreads), 0, stream, a);
+    launch_step_twin<27, 0ull>(a, stream);
   else if (nv == 18 && sweep_skip)
-    hipLaunchKernelGGL((k_step<18, kSweepSkip18>), dim3(blocks), dim3(kStepThreads), 0, stream, a);
+    launch_step_twin<18, kSweepSkip18>(a, stream);
   else if (nv == 18)
-    hipLaunchKernelGGL((k_step<18, 0ull>), dim3(blocks), dim3(kStepThreads), 0, stream, a);
+    launch_step_twin<18, 0ull>(a, stream);
   else
     return hipErrorInvalidValue;
   return hipGetLastError();

@@ -81,8 +81,9 @@ __device__ __forceinline__ float capsule_contact_sel(const float* a1, const floa
 //      stone-major, geom-minor;  2. every other geom against the candidate stones, likewise;
 //   3. robot self-contacts, one per self-collision pair in table order.
 // gcap: the largest pass-B group level (Consts::pair_group_cap); ts: the diagnostic pair / level counts.
+template <class TS>
 __device__ __forceinline__ int collide(const Consts& K, EnvS& s, int lane, int ncap, const GeomC& gc, const float* h,
-                                       float margin, int gcap, Stamp& ts) {
+                                       float margin, int gcap, TS& ts) {
   const as_model_t& m = K.model;
   const int nst = K.task.num_steps, ng = m.num_geoms, npri = m.num_priority_geoms, nsp = m.num_self_pairs;
   // self-collision pair words of this lane (pairs lane, lane + 32, ...), loaded first so that their

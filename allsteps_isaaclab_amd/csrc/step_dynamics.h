@@ -150,10 +150,14 @@ __device__ __forceinline__ void fk(KT& K, EnvS& s, int lane, const Topo& tp, Lin
   }
   if constexpr (kDyn) {
     if (lane == kZeroRow) {  // the walks' +0 rows (see take_bit_z)
+      // (the zero in a VGPR: as a scalar constant it was hoisted out of the substep loop, an SGPR held across
+      // every phase and spilled inside the loop)
+      float z = 0.f;
+      asm volatile("" : "+v"(z));
 #pragma unroll
-      for (int k = 0; k < 10; ++k) d.Ib[kZeroRow][k] = 0.f;
+      for (int k = 0; k < 10; ++k) d.Ib[kZeroRow][k] = z;
 #pragma unroll
-      for (int k = 0; k < 6; ++k) d.Sq[kZeroRow][k] = 0.f;
+      for (int k = 0; k < 6; ++k) d.Sq[kZeroRow][k] = z;
     }
   }
   if constexpr (kDyn) {
@@ -236,8 +240,10 @@ __device__ __forceinline__ float dynamics(const Consts& K, EnvS& s, int lane, co
     }
   }
   if (lane == kZeroRow) {  // the walks' +0 row (see take_bit_z); FK's Rl, which b aliases, is dead
+    float z = 0.f;  // (a VGPR zero, as in fk)
+    asm volatile("" : "+v"(z));
 #pragma unroll
-    for (int k = 0; k < 6; ++k) d.b.cr[kZeroRow][k] = 0.f;
+    for (int k = 0; k < 6; ++k) d.b.cr[kZeroRow][k] = z;
   }
   __syncthreads();
   float f[6], Ib[10];

@@ -133,9 +133,12 @@ __device__ __forceinline__ void half_min_n(float (&v)[N]) {
   }
 }
 
-// diagnostic phase stamps (off when p == nullptr): each wave accumulates its s_memtime deltas per
-// phase in LDS and adds them to the device counters once, at the end of the launch -- a global
-// atomic per phase boundary would put a contended memory round trip into the next phase.
+// diagnostic phase stamps, Stamp<kOn>.  k_step carries Stamp<false>: no members, empty methods, so the
+// production kernel holds no stamp pointer, counter, branch, clock read or LDS for them.  Its twin
+// k_step_diag carries Stamp<true> and is launched exactly when as_debug_stamps set a buffer (launch_step; p is
+// never null there): each wave accumulates its s_memtime deltas per phase in LDS and adds them to the device
+// counters once, at the end of the launch -- a global atomic per phase boundary would put a contended memory
+// round trip into the next phase.
 // With p[kWaveRecFlag] != 0 each wave also writes a record of its own (the last launch's waves:
 // phase cycles, total, start / end time, HW_ID / XCC_ID, rows and contacts summed over substeps per
 // env; collide's pass B: the stone pairs of each env, their sum over the substeps in bits 0-15 and the
@@ -145,7 +148,18 @@ __device__ __forceinline__ void half_min_n(float (&v)[N]) {
 // (scripts/stamps.py; the record's size and words are part of as_debug_stamps' contract, include/allsteps.h).
 constexpr int kWaveRecFlag = 31, kWaveRecBase = 64, kWaveRecWords = 30;
 static_assert(16 + kNumStamps <= kWaveRecFlag && kNumStamps + 14 <= kWaveRecWords, "stamp slots");
-struct Stamp {
+template <bool kOn>
+struct Stamp;
+template <>
+struct Stamp<false> {
+  __device__ __forceinline__ void start() {}
+  __device__ __forceinline__ void count(int, int) {}
+  __device__ __forceinline__ void pairs(int, int) {}
+  __device__ __forceinline__ void mark(int) {}
+  __device__ __forceinline__ void flush() {}
+};
+template <>
+struct Stamp<true> {
   unsigned long long* p;
   unsigned long long* acc;  // LDS, kNumStamps
   unsigned long long t;

@@ -157,8 +157,6 @@ enum { kPkIdx = 0, kPkPrev, kPkNext, kPkCount, kPkSwing, kPkEpLen, kPkPot, kPkOl
 struct Smem {
   EnvS env[EPB];
   Topo topo[G];  // per-lane tree plan (shared by both envs; registers cannot hold it)
-  unsigned long long stamp_acc[kNumStamps];
-  int maxrow;
 };
 
 }  // namespace as

@@ -214,9 +214,9 @@ __device__ __forceinline__ void pgs_sweeps(const EnvS& s, int iters, float& uj, 
   }
 }
 
-template <int NV, uint64_t SKIP>
+template <int NV, uint64_t SKIP, class TS>
 __device__ void substep(const Consts& K0, Smem& sm, EnvS& s, int lane0, const Topo& tp0, const GeomC& gc,
-                        const LinkC& lc, uint32_t (&mask_out)[4], Stamp& ts) {
+                        const LinkC& lc, uint32_t (&mask_out)[4], TS& ts) {
   // Opaque copies of the constants pointer and the lane id: everything derived from them below
   // (model-table loads, LDS addresses, lane masks) is loop-invariant, and without this the
   // compiler hoists all of it out of the substep loop and spills it.
@@ -226,8 +226,16 @@ __device__ void substep(const Consts& K0, Smem& sm, EnvS& s, int lane0, const To
   const Consts& K = *(const Consts*)(kp);
   const Topo& tp = tp0;  // LDS (Smem::topo)
   const as_model_t& m = K.model;
-  const float dt = K.sim.dt;
   const int nh = m.num_hinges;
+  // A fresh opaque copy of the constants pointer for the phases that read dt (u*, the rows, the integration):
+  // each loads its own dt, one short live range per phase.  One load at the top of the substep was held across
+  // the H rows' lane masks, the substep's SGPR peak, and spilled and reloaded inside the loop -- as was
+  // model.com[0], read by the first FK and again by the integration.
+  auto fresh = [kp]() -> const Consts& {
+    CK* q = kp;
+    asm volatile("" : "+s"(q));
+    return *(const Consts*)(q);
+  };
   // Scalars of the model loaded in groups just ahead of the phases that use them, each group passed
   // through an empty asm: one wait per group instead of a scalar load and a wait beside each use (a
   // wait on the scalar loads also waits on every LDS read in flight, so each one exposed an LDS
@@ -250,6 +258,7 @@ __device__ void substep(const Consts& K0, Smem& sm, EnvS& s, int lane0, const To
   float Hr[NP];
   h_row<NV>(s, lane, tp, gc.anc, Sj, Fj, *reinterpret_cast<float(*)[NV]>(Hr));
   ts.mark(kStDyn);
+  const float dt = fresh().sim.dt;  // (loaded here, under the sweep: u* below is its first use)
   {
     // into the sweep's round-0 column order with the identity pad rows / columns (register renaming),
     // the sweep, and back: row `lane` of H^-1 in dof order
@@ -265,6 +274,10 @@ __device__ void substep(const Consts& K0, Smem& sm, EnvS& s, int lane0, const To
     for (int k = NV; k < NP; ++k) Hr[k] = 0.f;
   }
   ts.mark(kStChol);
+  // (the lane id, opaque again here and ahead of the W rows and the integration: a lane mask formed in one phase
+  // -- lane < nh, lane >= 1 -- is formed again where a later phase tests it, one VALU compare, not held as an
+  // SGPR pair across the phases between and spilled inside the loop)
+  asm volatile("" : "+v"(lane));
   // u* = u + dt H^-1 b   (b broadcast from LDS)
   float uj = 0.f;
   {
@@ -436,6 +449,7 @@ __device__ void substep(const Consts& K0, Smem& sm, EnvS& s, int lane0, const To
   // W = H^-1 J^T, A_rr and the in-triplet couplings (w_rows: one row per lane); lane j's W and J
   // columns go to registers for the PGS.  Hr is zero on lanes >= NV.
   float Wc[MAXR], Jc[MAXR];
+  asm volatile("" : "+v"(lane));
   w_rows<NV>(s, lane, nrow, Hr, Jr, Jc, Wc, jmask);
   __syncthreads();
   ts.mark(kStWsolve);
@@ -448,7 +462,12 @@ __device__ void substep(const Consts& K0, Smem& sm, EnvS& s, int lane0, const To
   // row (J_s . (u + W_r dl_r) = J_s . u + A_sr dl_r) with one reduction latency per group instead
   // of one per row.  The row loop is unrolled with an exit per group; rows in [maxrow, group end)
   // have zero J / W / metadata and leave everything unchanged.
-  const int iters = K.sim.pgs_iters;
+  // (with the sweep count, in one group under the sweeps: the scalars of the flags and the integration)
+  const Consts& Ki = fresh();
+  const int iters = Ki.sim.pgs_iters;
+  const float dti = Ki.sim.dt, mjv = Ki.sim.max_joint_vel;
+  const int nhi = Ki.model.num_hinges;
+  const float com0[3] = {Ki.model.com[0][0], Ki.model.com[0][1], Ki.model.com[0][2]};
   float lamr[MAXR];
 #pragma unroll
   for (int r = 0; r < MAXR; ++r) lamr[r] = 0.f;
@@ -487,13 +506,14 @@ __device__ void substep(const Consts& K0, Smem& sm, EnvS& s, int lane0, const To
   // ---- contact-sensor flags of this substep (force_matrix_w = impulse / dt, > eps): lane c sums
   //      lambda_n n over the contacts with its (foot, stone) pair in ascending order, and the
   //      per-foot stone bits are OR-reduced over the half-wave
+  asm volatile("" : "+v"(lane));
   {
     // All MAXC terms (one 16-B read each; the terms past an env's own count add +0 to a sum that is
     // never -0: the same bits) and no per-count dispatch: the flags, the hind-feet masks (zero for a
     // biped) and the root update below are one basic block, so the scheduler interleaves the root
     // update's serial chain with the flag sums.
     uint32_t b[4] = {0u, 0u, 0u, 0u};
-    contact_flag<MAXC>(s, lane, nce, dt, b);
+    contact_flag<MAXC>(s, lane, nce, dti, b);
     half_or2(b[0], b[1]);
     half_or2(b[2], b[3]);
 #pragma unroll
@@ -505,16 +525,16 @@ __device__ void substep(const Consts& K0, Smem& sm, EnvS& s, int lane0, const To
   {
     const float* u = s.u;
     float c0w[3];
-    for (int k = 0; k < 3; ++k) c0w[k] = fmaf(dt, u[k], s.root_pos[k] + s.c0[k]);
+    for (int k = 0; k < 3; ++k) c0w[k] = fmaf(dti, u[k], s.root_pos[k] + s.c0[k]);
     const float* w = u + 3;
     const float wn = sqrtf(dot3(w, w));
-    const float th = wn * dt;
+    const float th = wn * dti;
     float sn, cs;
     as_sincosf(0.5f * th, &sn, &cs);
     const float sc = sn / wn;
     const bool big = th > 1e-12f;
-    const float dq[4] = {big ? cs : 1.f, big ? w[0] * sc : 0.5f * dt * w[0], big ? w[1] * sc : 0.5f * dt * w[1],
-                         big ? w[2] * sc : 0.5f * dt * w[2]};
+    const float dq[4] = {big ? cs : 1.f, big ? w[0] * sc : 0.5f * dti * w[0], big ? w[1] * sc : 0.5f * dti * w[1],
+                         big ? w[2] * sc : 0.5f * dti * w[2]};
     const float* q0 = s.root_quat;
     float nq[4] = {dq[0] * q0[0] - dq[1] * q0[1] - dq[2] * q0[2] - dq[3] * q0[3],
                    dq[0] * q0[1] + dq[1] * q0[0] + dq[2] * q0[3] - dq[3] * q0[2],
@@ -524,13 +544,13 @@ __device__ void substep(const Consts& K0, Smem& sm, EnvS& s, int lane0, const To
     for (int k = 0; k < 4; ++k) rq[k] = nq[k] * qn;
     float Rn[9], cl[3];
     quat_to_mat(rq, Rn);
-    matvec3(Rn, m.com[0], cl);
+    matvec3(Rn, com0, cl);
     for (int k = 0; k < 3; ++k) rp[k] = c0w[k] - cl[k];
   }
-  if (lane < nh) {
-    float v = fminf(fmaxf(s.u[6 + lane], -K.sim.max_joint_vel), K.sim.max_joint_vel);
+  if (lane < nhi) {
+    float v = fminf(fmaxf(s.u[6 + lane], -mjv), mjv);
     s.u[6 + lane] = v;
-    s.qi[lane] = fmaf(dt, v, s.qi[lane]);
+    s.qi[lane] = fmaf(dti, v, s.qi[lane]);
   }
   if (lane == 0) {
     for (int k = 0; k < 4; ++k) s.root_quat[k] = rq[k];
